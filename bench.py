@@ -3,11 +3,19 @@
 8 ppc, Yee FDTD, order-3 shape, Esirkepov, Boris, 1-pass bilinear filter; weak scaling for
 N>1: one 256^3 brick per GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one full PIC step of the hot path (gather+push, current deposition, filter +
 guard-cell sum, EvolveB/E/B, guard-cell fills, periodic wrap/sort) over every particle and
 cell resident in HBM.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, pre-rolls, warms up, times the K steps and prints the headline line.
+--full adds what takes extra work: the energy / particle-count sanity figures, the per-phase
+timer pass and the kernels / roofline tables built on it, the exchange statistics and the
+weak-scaling comparison of N > 1, and the CPU-oracle baseline.
+--dump-outputs DIR writes the state the K timed steps left (a fixed, seeded sample of the
+fields and particles, see dump_outputs) as DIR/<name>.npy, so that two builds can be
+compared output for output.
 """
 from __future__ import annotations
 
@@ -197,6 +205,55 @@ def cpu_baseline():
     return out
 
 
+FIELD_NAMES = ("Ex", "Ey", "Ez", "Bx", "By", "Bz", "jx", "jy", "jz")
+DUMP_FIELD_SAMPLES = 1 << 18      # per field component: 9 x 2 MiB
+DUMP_PARTICLE_SAMPLES = 1 << 18   # particles: 7 attributes x 2 MiB
+DUMP_SEED = 20240101
+
+
+def dump_outputs(sim, sid, out_dir, suffix=""):
+    """What the timed steps computed, as float64 .npy files in `out_dir` (about 34 MB; the same sample in every run of
+    the same arguments):
+      * <field>.npy for Ex..Bz, jx..jz: the values at a seeded sample of the brick's valid points, [i, j, k] drawn once
+        per field shape;
+      * <field>_sumsq.npy: the sum of squares over all valid points of each of those fields (one number each);
+      * particles.npy (7, n): x, y, z, w, ux, uy, uz of a seeded sample of the particles taken in the order of
+        increasing x (the cell sort leaves the order within a cell open, so storage order is not comparable).
+    A rank of a multi-brick run writes its own brick's share with `suffix` on every name."""
+    import numpy as np
+    import torch
+    from warpx_amd.distributed import _as_tensor
+    os.makedirs(out_dir, exist_ok=True)
+    on_device = str(sim.lib.memory).startswith("cuda")   # host memory on the CPU execution model of the tests
+    rng = np.random.default_rng(DUMP_SEED)
+    picks = {}
+    for name in FIELD_NAMES:
+        v = sim.field_view(name)
+        n, g = [int(x) for x in v.n], [int(x) for x in v.ng]
+        js, ks = int(v.jstride), int(v.kstride)
+        count = ks * n[2]
+        a = _as_tensor(int(v.p), 8 * count, on_device).view(torch.float64)
+        valid = [n[d] - 2 * g[d] for d in range(3)]
+        key = (tuple(n), tuple(g), js, ks)
+        if key not in picks:
+            ijk = [rng.integers(0, valid[d], DUMP_FIELD_SAMPLES) + g[d] for d in range(3)]
+            off = ijk[0] + ijk[1] * js + ijk[2] * ks
+            assert off.min() >= 0 and off.max() < count, (name, off.min(), off.max(), count)
+            picks[key] = torch.as_tensor(off, dtype=torch.int64, device=a.device)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a[picks[key]].cpu().numpy())
+        block = a[: count].view(n[2], n[1], js)[g[2]: n[2] - g[2], g[1]: n[1] - g[1], g[0]: n[0] - g[0]]
+        np.save(os.path.join(out_dir, f"{name}_sumsq{suffix}.npy"),
+                np.array([float(torch.sum(block * block))], dtype=np.float64))
+    v = sim.particle_view(sid)
+    npart = int(v.np)
+    arr = [_as_tensor(int(getattr(v, k)), 8 * npart, on_device).view(torch.float64)
+           for k in ("x", "y", "z", "w", "ux", "uy", "uz")]
+    order = torch.argsort(arr[0], stable=True)
+    ranks = np.unique(rng.integers(0, npart, min(DUMP_PARTICLE_SAMPLES, npart)))
+    sel = order[torch.as_tensor(ranks, dtype=torch.int64, device=order.device)]
+    np.save(os.path.join(out_dir, f"particles{suffix}.npy"), torch.stack([t[sel] for t in arr]).cpu().numpy())
+
+
 def stencil_microbench(sim, reps=20):
     """EvolveB / EvolveE launched `reps` times back to back on the simulation's own fields between
     one pair of events on the kernels' stream (dt = 0 leaves the fields unchanged): the per-launch
@@ -264,6 +321,12 @@ def main():
     ap.add_argument("--deposit-acc", choices=["f64", "f32"], default="f64",
                     help="accumulators of the LDS deposition tiles: f64 = ds_add_f64 (the parity build, the headline line); "
                          "f32 = ds_add_f32, the throughput variant of BASELINE.json's north_star (2e-6 gate)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beyond the headline: sanity, phase pass, kernels / roofline, exchange statistics, "
+                         "weak scaling (N > 1) and the CPU baseline (N = 1); --no-sanity, --no-phase-pass and "
+                         "--no-cpu-baseline drop single ones")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the timed steps (seeded sample of fields and particles) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-phase-pass", action="store_true")
     ap.add_argument("--sync-each-call", action="store_true",
@@ -279,6 +342,8 @@ def main():
                          "and bytes, instead of the bench line: separates 'RCCL is slow' from 'the step is slow' on a "
                          "first multi-GPU run")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline figure only
+        args.no_sanity = args.no_phase_pass = args.no_cpu_baseline = True
 
     import torch
     from warpx_amd import _capi, load_product, plasma
@@ -404,6 +469,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(sim, sid0, args.dump_outputs, f"_rank{rank}" if world > 1 else "")
 
     sanity = None
     if e_before is not None:
@@ -453,7 +520,7 @@ def main():
             transport.set_timing(False)
 
     comm_stats = None
-    if rccl:
+    if rccl and args.full:
         st = transport.stats()
         nsteps_head = max(sim.istep - nph, 1)
         comm_stats = {"transport": "rccl (in-library)", "exchanges_per_step": st_head["n_exchanges"] / nsteps_head,
@@ -464,7 +531,7 @@ def main():
                       "exchange_ms_per_step": st["timed_ms"] / max(nph, 1),
                       "note": "counts over the whole run up to the end of the timed steps; milliseconds from HIP events "
                               "around every exchange in the separate phase pass (rank 0)"}
-    elif transport is not None:
+    elif transport is not None and args.full:
         comm_stats = {"transport": "torch.distributed (Python callbacks)" + (", gloo, slabs staged through pinned host memory"
                                                                              if args.backend == "gloo" else ""),
                       "exchanges_per_step": transport.n_exchanges / max(sim.istep, 1),
@@ -476,7 +543,7 @@ def main():
         cps = total_cells * args.steps / elapsed
         kernels = {}
         dominant = None
-        traffic, traffic_note = pmc_traffic(args) if world == 1 else ({}, "N > 1")
+        traffic, traffic_note = (pmc_traffic(args) if world == 1 else ({}, "N > 1")) if args.full else ({}, "")
         sq_counters = traffic.pop("_sq", {})   # SQ passes of the shipped particle kernels, same file, same stamp
         micro = {} if args.no_phase_pass else stencil_microbench(sim)
         for name, (ms, cnt) in phases.items():
@@ -560,12 +627,13 @@ def main():
                        "preroll_steps": args.preroll, "overlap_halo": bool(sim.halo_overlap),
                        "momentum_synchronisation": "inside the timed region (Evolve(K) as one run)" if args.sync_each_call
                        else "outside the timed region (the K steps are consecutive steps of one longer run)"},
-            "roofline": roofline,
-            "kernels": kernels,
         }
+        if args.full:
+            out["roofline"] = roofline
+            out["kernels"] = kernels
         if comm_stats:
             out["exchange"] = comm_stats
-        if world > 1:
+        if world > 1 and args.full:
             # What the field exchanges of a step put on the wire at most (allocated guard depths; the named depths of the
             # exchanges are smaller or equal): per split direction two face slabs of E, B (FillBoundary) and J (SumBoundary).
             pred = 0.0

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=$(pwd)/gpurun_out/r6d; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q -k "sort_folded or bricks_on_one_gpu or overlapped or zero_multi or guard_layer or uniform_plasma_parity or as_processes" 2>&1 | tail -3 | tee $O/pytest.txt
 for merged in 1 0; do for si in 1 2 3 4; do
   [ $merged = 0 ] && [ $si = 1 ] && continue
-  WXA_SORT_MERGED=$merged timeout 300 python bench.py --steps 12 --warmup 6 --sort-interval $si --no-cpu-baseline > $O/tmp.json 2>/dev/null
+  WXA_SORT_MERGED=$merged timeout 300 python bench.py --full --steps 12 --warmup 6 --sort-interval $si --no-cpu-baseline > $O/tmp.json 2>/dev/null
   python -c "
 import json
 d=json.load(open('$O/tmp.json'))

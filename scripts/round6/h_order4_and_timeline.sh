@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=$(pwd)/gpurun_out/r6h; mkdir -p $O; ROOTDIR=$(pwd)
 timeout 900 python -m pytest tests -m gpu -x -q -k "gather_push_lds_tiles or deposit_current_lds_tiles or test_uniform_plasma_parity or esirkepov_continuity" 2>&1 | tail -3 | tee $O/pytest_order4.txt
 for o in 4 2 1; do
-timeout 300 python bench.py --steps 12 --warmup 6 --order $o --no-cpu-baseline --no-sanity > $O/tmp.json 2>/dev/null
+timeout 300 python bench.py --full --steps 12 --warmup 6 --order $o --no-cpu-baseline --no-sanity > $O/tmp.json 2>/dev/null
 python -c "
 import json
 d=json.load(open('$O/tmp.json'))

@@ -3,7 +3,7 @@
 # the free-flight position, rank from an LDS histogram, one 8-byte store per particle; nothing uses the result)
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=$(pwd)/gpurun_out/r6l; mkdir -p $O
 for rep in 1 2 3; do for v in "" "WXA_COUNT_PROBE=1"; do
-  env WXA_PRODUCT_LIB=warpx_amd/libwarpx_amd_probe.so $v timeout 300 python bench.py --steps 12 --warmup 6 --no-cpu-baseline --no-sanity > $O/tmp.json 2>/dev/null
+  env WXA_PRODUCT_LIB=warpx_amd/libwarpx_amd_probe.so $v timeout 300 python bench.py --full --steps 12 --warmup 6 --no-cpu-baseline --no-sanity > $O/tmp.json 2>/dev/null
   python -c "
 import json
 d=json.load(open('$O/tmp.json'))

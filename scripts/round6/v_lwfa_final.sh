@@ -13,7 +13,7 @@ print('config 5: ms/step %.2f, %.3e particle-steps/s, %.3e cell-updates/s, parti
 for k,v in d['kernels'].items(): print('  %-18s %.3f ms per launch, %.2f launches per step, %.3f ms per step %s' % (k, v['avg_ms'], v['launches_per_step'], v['ms_per_step'], ('hbm %.3f' % v['hbm_frac']) if 'hbm_frac' in v else ''))
 "
 done | tee $O/lwfa_boosted.txt
-timeout 300 python bench.py --steps 12 --warmup 6 --no-cpu-baseline --no-sanity > $O/tmp.json 2>/dev/null
+timeout 300 python bench.py --full --steps 12 --warmup 6 --no-cpu-baseline --no-sanity > $O/tmp.json 2>/dev/null
 python -c "
 import json
 d=json.load(open('$O/tmp.json'))

@@ -3,7 +3,7 @@
 # (WXA_HEAVY_TILE=100000 switches the unit table on without a heavy tile; WXA_TILE_INTERLEAVE picks the order)
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=$(pwd)/gpurun_out/r6zc; mkdir -p $O
 for v in "WXA_TILE_INTERLEAVE=0" "WXA_TILE_INTERLEAVE=1" "WXA_TILE_INTERLEAVE=0" "WXA_TILE_INTERLEAVE=1"; do
-  env WXA_HEAVY_TILE=100000 $v timeout 300 python bench.py --steps 12 --warmup 6 --no-cpu-baseline --no-sanity > $O/tmp.json 2>/dev/null
+  env WXA_HEAVY_TILE=100000 $v timeout 300 python bench.py --full --steps 12 --warmup 6 --no-cpu-baseline --no-sanity > $O/tmp.json 2>/dev/null
   python -c "
 import json
 d=json.load(open('$O/tmp.json'))

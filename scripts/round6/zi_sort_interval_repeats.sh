@@ -3,7 +3,7 @@
 # three of the four evidence sessions' single runs)
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; O=$(pwd)/gpurun_out/r6zi; mkdir -p $O
 for rep in 1 2 3; do for k in 2 3 4; do
-  timeout 300 python bench.py --steps 24 --warmup 12 --no-cpu-baseline --no-sanity --sort-interval $k > $O/tmp.json 2>/dev/null
+  timeout 300 python bench.py --full --steps 24 --warmup 12 --no-cpu-baseline --no-sanity --sort-interval $k > $O/tmp.json 2>/dev/null
   python -c "
 import json
 d=json.load(open('$O/tmp.json'))

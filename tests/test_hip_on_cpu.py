@@ -134,7 +134,7 @@ def test_bench_control_flow_on_several_ranks(n, port):
     import json
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port(port)), os.path.join(ROOT, "scripts", "bench_on_cpu.py"), "--gpus", str(n),
-           "--ncell", "16", "--steps", "3", "--warmup", "1", "--preroll", "2", "--no-cpu-baseline", "--n1-ms", "1.0"]
+           "--ncell", "16", "--steps", "3", "--warmup", "1", "--preroll", "2", "--full", "--no-cpu-baseline", "--n1-ms", "1.0"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -169,11 +169,11 @@ def test_boosted_wakefield_bench_control_flow_on_the_cpu_execution_model():
 
 
 def test_bench_control_flow_on_the_cpu_execution_model():
-    """bench.py, unmodified, through scripts/bench_on_cpu.py (tiny grid): the JSON line carries the contract's keys.
-    A dry run of the control flow only -- the numbers mean nothing."""
+    """bench.py --full, unmodified, through scripts/bench_on_cpu.py (tiny grid): the JSON line carries the contract's keys
+    and the per-phase tables.  A dry run of the control flow only -- the numbers mean nothing."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "bench_on_cpu.py"), "--ncell", "16", "--steps", "2",
-                        "--warmup", "1", "--preroll", "2", "--no-cpu-baseline"], cwd=ROOT, capture_output=True,
+                        "--warmup", "1", "--preroll", "2", "--full", "--no-cpu-baseline"], cwd=ROOT, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -182,3 +182,38 @@ def test_bench_control_flow_on_the_cpu_execution_model():
         assert key in line, key
     assert line["roofline"]["bound"] == "hbm" and line["config"]["workload"].startswith("3D uniform_plasma")
     assert {"EvolveB", "EvolveE", "GatherAndPush", "CurrentDeposition"} <= set(line["kernels"])
+
+
+def test_plain_bench_line_and_its_outputs_on_the_cpu_execution_model(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and prints the headline keys only; --dump-outputs
+    writes the state of the last timed step as float64 .npy files, the same sample in two runs of the same arguments."""
+    import json
+    import numpy as np
+    lines, dumps = [], []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "bench_on_cpu.py"), "--ncell", "16", "--steps", "3",
+                            "--warmup", "1", "--preroll", "2", "--dump-outputs", str(d)], cwd=ROOT, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dumps.append(d)
+    line = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["metric"] == "particle_steps_per_s" and line["unit"] == "particle-steps/s" and line["higher_is_better"]
+    assert line["steps"] == 3 and line["dtype"] == "f64" and line["ms_per_step"] > 0
+    assert abs(line["value"] - 16 ** 3 * 8 * 1e3 / line["ms_per_step"]) <= 1e-9 * line["value"]
+    for key in ("kernels", "roofline", "sanity", "cpu_baseline"):   # behind --full
+        assert key not in line, key
+    names = sorted(p.name for p in dumps[0].iterdir())
+    assert names == sorted(p.name for p in dumps[1].iterdir())
+    assert {"Ex.npy", "By.npy", "jz.npy", "Ez_sumsq.npy", "particles.npy"} <= set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(dumps[0] / name), np.load(dumps[1] / name)
+        total += (dumps[0] / name).stat().st_size
+        assert a.dtype == np.float64 and a.shape == b.shape and np.all(np.isfinite(a)), name
+        assert np.allclose(a, b, rtol=1e-9, atol=0.0), name
+    assert total <= 64 * 2 ** 20
+    assert np.load(dumps[0] / "particles.npy").shape[0] == 7 and np.max(np.abs(np.load(dumps[0] / "jx.npy"))) > 0

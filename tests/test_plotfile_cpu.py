@@ -3,9 +3,8 @@ reference's regression checksum": a deck runs on the CPU build of the host layer
 plotfile, and the checksum of Regression/Checksum/checksum.py:78-140 (sum |Q| per cell-centred field over the covering
 grid, sum |Q| per particle attribute, names with yt's `particle_` prefix) is recomputed FROM THE FILES and held against
 the reference's golden JSON.  The files are parsed twice: by a strict reader of the AMReX layouts written here after
-BTD_Plotfile_Header_Impl.cpp's own readers, and -- in this container, where /root/reference exists -- by the
-reference's Tools/PostProcessing/read_raw_data.py (its VisMF header / FAB reader), imported where it lies."""
-import importlib.util
+BTD_Plotfile_Header_Impl.cpp's own readers, and against what the reference's Tools/PostProcessing/read_raw_data.py (its
+VisMF header / FAB reader) read from the same run's plotfile (tests/golden/plotfile_reference_reader.json)."""
 import json
 import os
 import re
@@ -19,8 +18,6 @@ from tests.test_inputs_cpu import DECKS, HERE, compare_with_golden
 from tests.test_inputs_cpu import lib  # noqa: F401  (fixture)
 from warpx_amd.sim import WarpXSim
 from tests.ports import free_port
-
-REFERENCE = "/root/reference"
 
 
 def _read_box(text):
@@ -145,25 +142,33 @@ def test_plotfile_carries_the_golden_checksums(lib, tmp_path, deck, golden):  # 
     assert pf["step"] == sim.max_step
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference checkout is not on this machine")
 def test_the_reference_reader_opens_the_field_data(lib, tmp_path):  # noqa: F811
-    """Tools/PostProcessing/read_raw_data.py (the reference's own VisMF / FAB reader) on Level_0/Cell_H."""
-    spec = importlib.util.spec_from_file_location("ref_read_raw_data", os.path.join(REFERENCE, "Tools/PostProcessing/read_raw_data.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    if not hasattr(np, "product"):
-        np.product = np.prod   # the reference tool predates numpy 2
+    """Tools/PostProcessing/read_raw_data.py (the reference's own VisMF / FAB reader) on Level_0/Cell_H, as recorded in
+    tests/golden/plotfile_reference_reader.json by tests/golden/make_plotfile_reader_golden.py: the plotfile of the same
+    run has the header, boxes, files and offsets that reader found, and every field the values it read."""
+    gold = json.load(open(os.path.join(HERE, "golden", "plotfile_reference_reader.json")))
     sim = WarpXSim.from_inputs(lib, os.path.join(DECKS, "langmuir_multi_3d.inputs"))
     sim.evolve(4)
     plt = str(tmp_path / "plt")
     sim.write_plotfile(plt)
     sim.close()
     mine = read_plotfile(plt)
-    boxes, file_names, offsets, header = ref._read_header(os.path.join(plt, "Level_0", "Cell_H"))
-    assert header.version == 1 and header.ncomp == len(mine["names"]) and file_names == ["Cell_D_00000"]
-    theirs = ref._read_buffer(plt, os.path.join(plt, "Level_0", "Cell_H"), mine["names"])
-    for n in mine["names"]:
-        assert np.array_equal(theirs[n], mine["fields"][n]), n
+    ch = open(os.path.join(plt, "Level_0", "Cell_H")).read().split("\n")
+    head = gold["header"]
+    assert (int(ch[0]), int(ch[1]), int(ch[2])) == (head["version"], head["how"], head["ncomp"]) == (1, 1, len(mine["names"]))
+    assert [int(v) for v in ch[3].strip("()").split(",")] == head["nghost"]
+    nb = int(re.match(r"\((\d+) ", ch[4]).group(1))
+    boxes = [_read_box(ch[5 + i]) for i in range(nb)]
+    assert [[lo.tolist(), hi.tolist()] for lo, hi, _ in boxes] == gold["boxes"]
+    fod = [ch[7 + nb + i].split() for i in range(nb)]
+    assert [f[1] for f in fod] == gold["file_names"] and [int(f[2]) for f in fod] == gold["offsets"]
+    assert sorted(gold["fields"]) == sorted(mine["names"])
+    for n, g in gold["fields"].items():
+        a = mine["fields"][n]
+        assert list(a.shape) == g["shape"], n
+        assert abs(np.sum(np.abs(a)) - g["sum_abs"]) <= 1e-9 * g["sum_abs"], n
+        assert abs(np.max(np.abs(a)) - g["max_abs"]) <= 1e-9 * g["max_abs"], n
+        assert abs(np.sum(a) - g["sum"]) <= 1e-9 * g["sum_abs"], n
     assert np.max(np.abs(mine["fields"]["Ex"])) > 0
 
 
