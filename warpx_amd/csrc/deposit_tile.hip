@@ -19,9 +19,9 @@
 // domain before the periodic wrap) are queued and deposited with global atomics by a second kernel, so correctness
 // never depends on the sort being fresh.  DESIGN.md section 3 has the measurements behind each step.
 #include "deposit_body.hpp"
+#include "dispatch.hpp"
 #include "gather_body.hpp"
-#include "heavy_tiles.hpp"
-#include "workspace.hpp"
+#include "tile_launch.hpp"
 
 #include <stdlib.h>
 #include <algorithm>
@@ -121,22 +121,10 @@ struct JTriple {
     DevF x, y, z;
 };
 
-struct TileGeom {
-    int nt[3];        // tiles per direction
-    int cell_lo[3];   // global index of the brick's first cell
-};
-
 constexpr int NBANK = 16;         // LDS banks (8-byte wide) seen by one step of a ds_add_f64
 
-// Particles whose stencil leaves the LDS tile (stale sort, particles outside the domain before
-// the periodic wrap) are queued and deposited by deposit_stragglers_kernel with global atomics:
-// keeping that path out of the tile kernel saves registers and instruction cache.
-struct StragglerQueue {
-    int* __restrict__ idx;
-    unsigned* __restrict__ count;
-    unsigned* __restrict__ next = nullptr;   // the next launch's counter, zeroed by this one (wxa::flip_counter)
-    __device__ __forceinline__ void push(int ip) const { idx[atomicAdd(count, 1u)] = ip; }
-};
+// Particles whose stencil leaves the LDS tile are queued (StragglerQueue, tile_launch.hpp) and deposited by
+// deposit_stragglers_kernel with global atomics.
 
 __device__ __forceinline__ int frame_key(int li, int lj, int lk) { return li | (lj << 4) | (lk << 8); }
 
@@ -905,10 +893,6 @@ deposit_stragglers_kernel(const double* __restrict__ px, const double* __restric
     }
 }
 
-bool deposit_tile_available(const wxa_workspace* ws, const wxa_particle_view* p) {
-    return ws && ws->sorted_valid && ws->sorted_x == p->x && ws->sorted_np <= p->np;
-}
-
 // One extra LDS point per side beyond the exact stencil reach (M = 1): particles may have drifted up
 // to one cell since the last sort (sort_intervals > 1) before they have to take the
 // straggler path (global atomics, ~7 ns per particle).
@@ -917,31 +901,16 @@ constexpr int MARGIN = 1;
 template <int O, class CFG>
 static wxa_status launch_rows(const wxa_particle_view* p, const wxa_field_view J[3], const wxa_grid_geom* geom,
                                double q, double dt, double relative_time, wxa_workspace* ws, hipStream_t st) {
-    TileGeom tg;
-    for (int d = 0; d < 3; ++d) {
-        tg.nt[d] = (ws->sort_nc[d] + TS - 1) / TS;
-        tg.cell_lo[d] = ws->sort_cell_lo[d];
-    }
-    const long nunits = (long)tg.nt[0] * tg.nt[1] * tg.nt[2];
-    const Geom g = make_geom(*geom);
-    const int* offsets = (const int*)ws->offsets.p;
+    TileLaunch tl;
     wxa_status rc;
-    // tiles with far more particles than the others are shared by several workgroups (heavy_tiles.hpp)
-    HeavyUnits hu;
-    long extra_groups = 0;
-    if ((rc = plan_heavy_tiles(ws, offsets, nunits, (long)p->np, hu, extra_groups, st)) != WXA_OK) return rc;
-    const dim3 grid((unsigned)(xcd_grid_size(nunits) + extra_groups)), block(CFG::NT);
-    if ((rc = ws->stragglers.reserve(sizeof(int) * (size_t)p->np + 64)) != WXA_OK) return rc;
-    StragglerQueue sq{(int*)ws->stragglers.p, nullptr, nullptr};
-    unsigned *cnt_now = nullptr, *cnt_next = nullptr;
-    if ((rc = flip_counter(ws, 0, ws->deposit_flips, st, cnt_now, cnt_next)) != WXA_OK) return rc;   // words 0, 1 of ws->counters
-    sq.count = cnt_now; sq.next = cnt_next;
+    if ((rc = plan_tile_launch(ws, (long)p->np, 0, ws->deposit_flips, st, tl)) != WXA_OK) return rc;   // words 0, 1 of ws->counters
+    const Geom g = make_geom(*geom);
     const DevF jx = make_devf(J[0]), jy = make_devf(J[1]), jz = make_devf(J[2]);
     const EsirkepovStep es = make_esirkepov_step(g, dt, relative_time);
-    hipLaunchKernelGGL((deposit_tile_rows_kernel<O, MARGIN, CFG>), grid, block, 0, st, JTriple{jx, jy, jz}, p->x, p->y, p->z, p->w,
-                       p->ux, p->uy, p->uz, offsets, g, tg, q, es, relative_time, sq, hu);
-    hipLaunchKernelGGL((deposit_stragglers_kernel<O, CFG::ALGO>), dim3(512), dim3(256), 0, st, p->x, p->y,
-                       p->z, p->w, p->ux, p->uy, p->uz, sq.idx, sq.count, jx, jy, jz, g, q, es, relative_time);
+    hipLaunchKernelGGL((deposit_tile_rows_kernel<O, MARGIN, CFG>), dim3(tl.groups), dim3(CFG::NT), 0, st, JTriple{jx, jy, jz}, p->x,
+                       p->y, p->z, p->w, p->ux, p->uy, p->uz, tl.offsets, g, tl.tg, q, es, relative_time, tl.sq, tl.hu);
+    hipLaunchKernelGGL((deposit_stragglers_kernel<O, CFG::ALGO>), dim3(WXA_STRAGGLER_BLOCKS), dim3(256), 0, st, p->x, p->y,
+                       p->z, p->w, p->ux, p->uy, p->uz, tl.sq.idx, tl.sq.count, jx, jy, jz, g, q, es, relative_time);
     WXA_LAUNCH_CHECK();
     return WXA_OK;
 }
@@ -959,30 +928,30 @@ using RowsEsirkepovStreaming = RowsCfg<768, 3, double, WXA_DEPOSIT_ESIRKEPOV, 1>
 wxa_status deposit_current_tiled(const wxa_particle_view* p, const wxa_field_view J[3], const wxa_grid_geom* geom,
                                  double q, double dt, double relative_time, int order, int algo,
                                  wxa_workspace* ws, hipStream_t st) {
+    // order 4 (round 6): the tile's 15 points per direction are exactly the reach of the quartic stencil around a tile
+    // (nodes c - 2 .. c + 3 of the particle's cell c, one more each way for the old position) -- no point of drift
+    // margin is left, so a particle that has left its sort cell by more than the stencil's slack goes to the
+    // global-atomics pass; everything else deposits on the tile like the other even order
+    auto orders_1_to_4 = [&](auto cfg) {
+        return with_int<1, 2, 4, 3>(order, [&](auto o) {   // (3 last, like the ladder this replaces: the kernels keep their order in the code object)
+            return launch_rows<decltype(o)::value, decltype(cfg)>(p, J, geom, q, dt, relative_time, ws, st);
+        });
+    };
+    // WRONG, kept as it is: these two configurations have no order-4 kernel, and order 4 -- which
+    // wxa_deposit_current accepts -- is deposited by them with the ORDER-3 shapes (3 is listed last: it takes every other
+    // value).  The next pull request's to fix, with the order-4 cases the ADVICE asks for: it changes results.
+    auto orders_1_to_3_and_4_as_3 = [&](auto cfg) {
+        return with_int<1, 2, 3>(order, [&](auto o) {
+            return launch_rows<decltype(o)::value, decltype(cfg)>(p, J, geom, q, dt, relative_time, ws, st);
+        });
+    };
     if (algo == WXA_DEPOSIT_ESIRKEPOV) {
-        if (ws->deposit_accumulator == WXA_ACC_FP32) {
-            if (order == 1) return launch_rows<1, RowsEsirkepovF32>(p, J, geom, q, dt, relative_time, ws, st);
-            if (order == 2) return launch_rows<2, RowsEsirkepovF32>(p, J, geom, q, dt, relative_time, ws, st);
-            return launch_rows<3, RowsEsirkepovF32>(p, J, geom, q, dt, relative_time, ws, st);
-        }
-        if (ws->streaming_plasma) {   // wxa_workspace_set_streaming_plasma: most particles cross a cell per step
-            if (order == 1) return launch_rows<1, RowsEsirkepovStreaming>(p, J, geom, q, dt, relative_time, ws, st);
-            if (order == 2) return launch_rows<2, RowsEsirkepovStreaming>(p, J, geom, q, dt, relative_time, ws, st);
-            return launch_rows<3, RowsEsirkepovStreaming>(p, J, geom, q, dt, relative_time, ws, st);
-        }
-        if (order == 1) return launch_rows<1, RowsEsirkepov>(p, J, geom, q, dt, relative_time, ws, st);
-        if (order == 2) return launch_rows<2, RowsEsirkepov>(p, J, geom, q, dt, relative_time, ws, st);
-        // order 4 (round 6): the tile's 15 points per direction are exactly the reach of the quartic stencil around a tile
-        // (nodes c - 2 .. c + 3 of the particle's cell c, one more each way for the old position) -- no point of drift
-        // margin is left, so a particle that has left its sort cell by more than the stencil's slack goes to the
-        // global-atomics pass; everything else deposits on the tile like the other even order
-        if (order == 4) return launch_rows<4, RowsEsirkepov>(p, J, geom, q, dt, relative_time, ws, st);
-        return launch_rows<3, RowsEsirkepov>(p, J, geom, q, dt, relative_time, ws, st);
+        if (ws->deposit_accumulator == WXA_ACC_FP32) return orders_1_to_3_and_4_as_3(RowsEsirkepovF32{});
+        // wxa_workspace_set_streaming_plasma: most particles cross a cell per step
+        if (ws->streaming_plasma) return orders_1_to_3_and_4_as_3(RowsEsirkepovStreaming{});
+        return orders_1_to_4(RowsEsirkepov{});
     }
-    if (order == 1) return launch_rows<1, RowsDirect>(p, J, geom, q, dt, relative_time, ws, st);
-    if (order == 2) return launch_rows<2, RowsDirect>(p, J, geom, q, dt, relative_time, ws, st);
-    if (order == 4) return launch_rows<4, RowsDirect>(p, J, geom, q, dt, relative_time, ws, st);
-    return launch_rows<3, RowsDirect>(p, J, geom, q, dt, relative_time, ws, st);
+    return orders_1_to_4(RowsDirect{});
 }
 
 }  // namespace wxa

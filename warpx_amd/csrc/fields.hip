@@ -282,7 +282,6 @@ evolve_b_faces_kernel(DevF Ex, DevF Ey, DevF Ez, DevF Bx, DevF By, DevF Bz, Face
         *bz = *bz + (dt * (idy * (ex[Ex.js] - ex[0])) - dt * (idx * (ey[1] - ey[0])));
     }
 }
-#define WXA_STENCIL_DISPATCH(CALL) CALL(StProduction);
 
 // generic box copy kernels -----------------------------------------------------
 struct BoxN {
@@ -927,17 +926,12 @@ wxa_status wxa_evolve_b(const wxa_field_view E[3], const wxa_field_view B[3], do
         ub.lo[d] = std::min(bx.lo[d], std::min(by.lo[d], bz.lo[d]));
         ub.hi[d] = std::max(bx.hi[d], std::max(by.hi[d], bz.hi[d]));
     }
-#define WXA_LAUNCH_B(CFG)                                                                                       \
-    do {                                                                                                        \
-        const TileGrid tg = make_tiles_cfg<CFG>(ub);                                                            \
-        if (tg.ntiles > 0)                                                                                      \
-            hipLaunchKernelGGL((evolve_b_kernel<CFG>), dim3((unsigned)xcd_grid_size(tg.ntiles)),                \
-                               dim3(CFG::TI, CFG::TJ), 0, (hipStream_t)stream, make_devf(E[0]), make_devf(E[1]), \
-                               make_devf(E[2]), make_devf(B[0]), make_devf(B[1]), make_devf(B[2]), ub, bx, by,  \
-                               bz, tg, dt, dinv[0], dinv[1], dinv[2]);                                          \
-    } while (0)
-    WXA_STENCIL_DISPATCH(WXA_LAUNCH_B)
-#undef WXA_LAUNCH_B
+    using CFG = StProduction;
+    const TileGrid tg = make_tiles_cfg<CFG>(ub);
+    if (tg.ntiles > 0)
+        hipLaunchKernelGGL((evolve_b_kernel<CFG>), dim3((unsigned)xcd_grid_size(tg.ntiles)), dim3(CFG::TI, CFG::TJ), 0,
+                           (hipStream_t)stream, make_devf(E[0]), make_devf(E[1]), make_devf(E[2]), make_devf(B[0]),
+                           make_devf(B[1]), make_devf(B[2]), ub, bx, by, bz, tg, dt, dinv[0], dinv[1], dinv[2]);
     WXA_LAUNCH_CHECK();
     return WXA_OK;
 }
@@ -1033,17 +1027,11 @@ wxa_status wxa_evolve_b_ckc(const wxa_field_view E[3], const wxa_field_view B[3]
     }
     CkcCoefs cc;
     for (int n = 0; n < 5; ++n) { cc.x[n] = cx[n]; cc.y[n] = cy[n]; cc.z[n] = cz[n]; }
-    {
-#define WXA_CKC_LAUNCH(CFG)                                                                                            \
-    do {                                                                                                               \
-        const TileGrid tg = make_tiles_cfg<StencilCfg<1, CFG::TJ, CFG::KC, 1>>(ub);                                    \
-        hipLaunchKernelGGL(evolve_b_ckc_tiled_kernel<CFG>, dim3((unsigned)xcd_grid_size(tg.ntiles)), dim3(CFG::TI, CFG::TJ), \
-                           0, (hipStream_t)stream, make_devf(E[0]), make_devf(E[1]), make_devf(E[2]), make_devf(B[0]),    \
-                           make_devf(B[1]), make_devf(B[2]), ub, bx, by, bz, tg, dt, cc);                              \
-    } while (0)
-        WXA_CKC_LAUNCH(CkcProduction);
-#undef WXA_CKC_LAUNCH
-    }
+    using CFG = CkcProduction;
+    const TileGrid tg = make_tiles_cfg<StencilCfg<1, CFG::TJ, CFG::KC, 1>>(ub);
+    hipLaunchKernelGGL(evolve_b_ckc_tiled_kernel<CFG>, dim3((unsigned)xcd_grid_size(tg.ntiles)), dim3(CFG::TI, CFG::TJ), 0,
+                       (hipStream_t)stream, make_devf(E[0]), make_devf(E[1]), make_devf(E[2]), make_devf(B[0]), make_devf(B[1]),
+                       make_devf(B[2]), ub, bx, by, bz, tg, dt, cc);
     WXA_LAUNCH_CHECK();
     return WXA_OK;
 }
@@ -1070,18 +1058,13 @@ wxa_status wxa_evolve_e(const wxa_field_view E[3], const wxa_field_view B[3], co
         ub.lo[d] = std::min(bx.lo[d], std::min(by.lo[d], bz.lo[d]));
         ub.hi[d] = std::max(bx.hi[d], std::max(by.hi[d], bz.hi[d]));
     }
-#define WXA_LAUNCH_E(CFG)                                                                                       \
-    do {                                                                                                        \
-        const TileGrid tg = make_tiles_cfg<CFG>(ub);                                                            \
-        if (tg.ntiles > 0)                                                                                      \
-            hipLaunchKernelGGL((evolve_e_kernel<CFG>), dim3((unsigned)xcd_grid_size(tg.ntiles)),                \
-                               dim3(CFG::TI, CFG::TJ), 0, (hipStream_t)stream, make_devf(E[0]), make_devf(E[1]), \
-                               make_devf(E[2]), make_devf(B[0]), make_devf(B[1]), make_devf(B[2]),              \
-                               make_devf(J[0]), make_devf(J[1]), make_devf(J[2]), ub, bx, by, bz, tg, dt,       \
-                               dinv[0], dinv[1], dinv[2]);                                                      \
-    } while (0)
-    WXA_STENCIL_DISPATCH(WXA_LAUNCH_E)
-#undef WXA_LAUNCH_E
+    using CFG = StProduction;
+    const TileGrid tg = make_tiles_cfg<CFG>(ub);
+    if (tg.ntiles > 0)
+        hipLaunchKernelGGL((evolve_e_kernel<CFG>), dim3((unsigned)xcd_grid_size(tg.ntiles)), dim3(CFG::TI, CFG::TJ), 0,
+                           (hipStream_t)stream, make_devf(E[0]), make_devf(E[1]), make_devf(E[2]), make_devf(B[0]),
+                           make_devf(B[1]), make_devf(B[2]), make_devf(J[0]), make_devf(J[1]), make_devf(J[2]), ub, bx, by, bz,
+                           tg, dt, dinv[0], dinv[1], dinv[2]);
     WXA_LAUNCH_CHECK();
     return WXA_OK;
 }

@@ -16,19 +16,13 @@
 // momentum loaded together with its position instead of after the gather (hand-issued loads), no change; two particles of a
 // cell per lane sharing the LDS reads, 9.95.  Counters, profiles/round2/r2g_pmc_128cube_gather_tile_kernel.txt: 8 LDS
 // cycles per ds instruction and 0.2 % bank conflicts, the LDS busy 60 % and the VALU 50 % of the kernel's time.)
+#include "dispatch.hpp"
 #include "gather_body.hpp"
-#include "heavy_tiles.hpp"
 #include "push_sort.hpp"
-#include "workspace.hpp"
+#include "tile_launch.hpp"
 
 #include <stdlib.h>
 
-#ifndef WXA_STRAGGLER_BLOCKS
-// workgroups of 256 lanes of gather_push_stragglers_kernel (a grid-stride loop over a list whose length only the device
-// knows).  512 workgroups are two waves per SIMD; 2048 were measured and change nothing (0.19-0.62 ms per launch either
-// way at 256^3 x 8 per cell, profiles/round5/README.md): the kernel is not short of waves in flight
-#define WXA_STRAGGLER_BLOCKS 512
-#endif
 namespace wxa {
 
 // Clocks of the tile kernel (opt-in build, -DWXA_GATHER_PROFILE; read with scripts/gather_profile.py): thread 0 of every
@@ -73,23 +67,11 @@ struct SplitTile {
     static constexpr int total() { return off(6); }
 };
 
-struct GTileGeom {
-    int nt[3];
-    int cell_lo[3];
-};
-
 template <int N>
 struct LdsField {
     const double* base;
     __device__ __forceinline__ const double* at(int i, int j, int k) const { return base + i + N * (j + N * k); }
     static constexpr long js = N, ks = N * N;
-};
-
-struct GatherStragglers {
-    int* __restrict__ idx;
-    unsigned* __restrict__ count;
-    unsigned* __restrict__ next = nullptr;   // the next launch's counter, zeroed by this one (wxa::flip_counter)
-    __device__ __forceinline__ void push(int ip) const { idx[atomicAdd(count, 1u)] = ip; }
 };
 
 template <int PUSHER, bool MOVE>
@@ -117,7 +99,7 @@ __device__ __forceinline__ void push_and_store(const PV& p, int ip, double xp, d
 template <int O, int G, int PUSHER, bool MOVE, int PART = 0>
 __global__ void __launch_bounds__(GT_THREADS) WXA_WAVES_PER_SIMD(O <= 3 ? 4 : 2)   // what the staged tile lets a CU hold
 gather_push_tile_kernel(PV p, const int* __restrict__ offsets, DevF Ex, DevF Ey, DevF Ez, DevF Bx, DevF By,
-                        DevF Bz, Geom g, GTileGeom tg, double q, double m, double dt, GatherStragglers sq, ExtEB ext,
+                        DevF Bz, Geom g, TileGeom tg, double q, double m, double dt, StragglerQueue sq, ExtEB ext,
                         PushSort hook, HeavyUnits hu) {
     constexpr int N = GatherTileDims<G, O>::N;
     constexpr int NPTS = GatherTileDims<G, O>::NPTS;
@@ -374,91 +356,35 @@ gather_push_stragglers_kernel(PV p, const int* __restrict__ idx, const unsigned*
     }
 }
 
-bool gather_tile_available(const wxa_workspace* ws, const wxa_particle_view* p) {
-    return ws && ws->sorted_valid && ws->sorted_x == p->x && ws->sorted_np <= p->np;
-}
-
-template <int PUSHER, bool MOVE, int PART = 0>
-static wxa_status launch(const wxa_particle_view* p, const wxa_field_view E[3], const wxa_field_view B[3],
-                         const wxa_grid_geom* geom, double q, double m, double dt, int order, int galerkin,
-                         wxa_workspace* ws, hipStream_t st) {
-    GTileGeom tg;
-    for (int d = 0; d < 3; ++d) {
-        tg.nt[d] = (ws->sort_nc[d] + GT_TS - 1) / GT_TS;
-        tg.cell_lo[d] = ws->sort_cell_lo[d];
-    }
-    const long ntiles = (long)tg.nt[0] * tg.nt[1] * tg.nt[2];
-    const PV pv = make_pv(*p);
-    const Geom g = make_geom(*geom);
-    const int* offsets = (const int*)ws->offsets.p;
-    const DevF ex = make_devf(E[0]), ey = make_devf(E[1]), ez = make_devf(E[2]);
-    const DevF bx = make_devf(B[0]), by = make_devf(B[1]), bz = make_devf(B[2]);
-    wxa_status rc;
-    if ((rc = ws->stragglers.reserve(sizeof(int) * (size_t)p->np + 64)) != WXA_OK) return rc;
-    GatherStragglers sq{(int*)ws->stragglers.p, nullptr, nullptr};
-    unsigned *cnt_now = nullptr, *cnt_next = nullptr;
-    if ((rc = flip_counter(ws, 16, ws->gather_flips, st, cnt_now, cnt_next)) != WXA_OK) return rc;
-    sq.count = cnt_now; sq.next = cnt_next;   // words 16, 17 of ws->counters
-    const ExtEB ext = ext_of(ws);
-    const PushSort hook = make_push_sort(ws, 0, MOVE);
-    HeavyUnits hu;
-    long extra_groups = 0;
-    if ((rc = plan_heavy_tiles(ws, offsets, ntiles, (long)p->np, hu, extra_groups, st)) != WXA_OK) return rc;
-    const dim3 grid((unsigned)(xcd_grid_size(ntiles) + extra_groups)), block(GT_THREADS);
-#define WXA_GT(O, G)                                                                                        \
-    do {                                                                                                    \
-        hipLaunchKernelGGL((gather_push_tile_kernel<O, G, PUSHER, MOVE, PART>), grid, block, 0, st, pv, offsets, ex, \
-                           ey, ez, bx, by, bz, g, tg, q, m, dt, sq, ext, hook, hu);                                   \
-        hipLaunchKernelGGL((gather_push_stragglers_kernel<O, G, PUSHER, MOVE>), dim3(WXA_STRAGGLER_BLOCKS), dim3(256), 0, st, pv, \
-                           sq.idx, sq.count, ex, ey, ez, bx, by, bz, g, q, m, dt, ext, hook);                     \
-    } while (0)
-    if (galerkin) {
-        if (order == 1) WXA_GT(1, 1); else if (order == 2) WXA_GT(2, 1); else if (order == 3) WXA_GT(3, 1); else WXA_GT(4, 1);
-    } else {
-        if (order == 1) WXA_GT(1, 0); else if (order == 2) WXA_GT(2, 0); else if (order == 3) WXA_GT(3, 0); else WXA_GT(4, 0);
-    }
-#undef WXA_GT
-    WXA_LAUNCH_CHECK();
-    return WXA_OK;
-}
-
+// part = 0: every tile; PushPX on one part of the tiles (part = 1 interior, 2 faces; move set), see the kernel
 wxa_status gather_push_tiled(const wxa_particle_view* p, const wxa_field_view E[3], const wxa_field_view B[3],
                              const wxa_grid_geom* geom, double q, double m, double dt, int order, int galerkin,
-                             int pusher, bool move, wxa_workspace* ws, hipStream_t st) {
-    if (pusher == WXA_PUSHER_BORIS) {
-        if (move) return launch<WXA_PUSHER_BORIS, true>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-        return launch<WXA_PUSHER_BORIS, false>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-    }
-    if (pusher == WXA_PUSHER_VAY) {
-        if (move) return launch<WXA_PUSHER_VAY, true>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-        return launch<WXA_PUSHER_VAY, false>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-    }
-    if (pusher == WXA_PUSHER_HC) {
-        if (move) return launch<WXA_PUSHER_HC, true>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-        return launch<WXA_PUSHER_HC, false>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-    }
-    if (move) return launch<WXA_PUSHER_BORIS_RR, true>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-    return launch<WXA_PUSHER_BORIS_RR, false>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-}
-
-// PushPX on one part of the tiles (part = 1 interior, 2 faces), see the kernel
-wxa_status gather_push_tiled_part(const wxa_particle_view* p, const wxa_field_view E[3], const wxa_field_view B[3],
-                                  const wxa_grid_geom* geom, double q, double m, double dt, int order, int galerkin,
-                                  int pusher, int part, wxa_workspace* ws, hipStream_t st) {
-    if (pusher == WXA_PUSHER_BORIS) {
-        if (part == 1) return launch<WXA_PUSHER_BORIS, true, 1>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-        return launch<WXA_PUSHER_BORIS, true, 2>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-    }
-    if (pusher == WXA_PUSHER_VAY) {
-        if (part == 1) return launch<WXA_PUSHER_VAY, true, 1>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-        return launch<WXA_PUSHER_VAY, true, 2>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-    }
-    if (pusher == WXA_PUSHER_HC) {
-        if (part == 1) return launch<WXA_PUSHER_HC, true, 1>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-        return launch<WXA_PUSHER_HC, true, 2>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-    }
-    if (part == 1) return launch<WXA_PUSHER_BORIS_RR, true, 1>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
-    return launch<WXA_PUSHER_BORIS_RR, true, 2>(p, E, B, geom, q, m, dt, order, galerkin, ws, st);
+                             int pusher, bool move, int part, wxa_workspace* ws, hipStream_t st) {
+    TileLaunch tl;
+    wxa_status rc;
+    if ((rc = plan_tile_launch(ws, (long)p->np, 16, ws->gather_flips, st, tl)) != WXA_OK) return rc;   // words 16, 17 of ws->counters
+    const PV pv = make_pv(*p);
+    const Geom g = make_geom(*geom);
+    const DevF ex = make_devf(E[0]), ey = make_devf(E[1]), ez = make_devf(E[2]);
+    const DevF bx = make_devf(B[0]), by = make_devf(B[1]), bz = make_devf(B[2]);
+    const ExtEB ext = ext_of(ws);
+    const PushSort hook = make_push_sort(ws, 0, move);
+    // what is pushed where: 0 PushP on every tile; PushPX on 1 every tile, 2 the interior tiles, 3 the tiles on a face
+    // (the parts exist for PushPX alone: no <..., MOVE = false, PART != 0> kernels)
+    with_int<0, 1, 2, 3>(move ? 1 + part : 0, [&](auto what) {
+    with_int<WXA_PUSHER_BORIS, WXA_PUSHER_VAY, WXA_PUSHER_HC, WXA_PUSHER_BORIS_RR>(pusher, [&](auto pu) {
+    with_int<1, 2, 3, 4>(order, [&](auto o) {
+    with_int<1, 0>(galerkin, [&](auto gk) {
+        constexpr int O = decltype(o)::value, G = decltype(gk)::value, PUSHER = decltype(pu)::value;
+        constexpr bool MOVE = decltype(what)::value != 0;
+        constexpr int PART = MOVE ? decltype(what)::value - 1 : 0;
+        hipLaunchKernelGGL((gather_push_tile_kernel<O, G, PUSHER, MOVE, PART>), dim3(tl.groups), dim3(GT_THREADS), 0, st, pv,
+                           tl.offsets, ex, ey, ez, bx, by, bz, g, tl.tg, q, m, dt, tl.sq, ext, hook, tl.hu);
+        hipLaunchKernelGGL((gather_push_stragglers_kernel<O, G, PUSHER, MOVE>), dim3(WXA_STRAGGLER_BLOCKS), dim3(256), 0, st,
+                           pv, tl.sq.idx, tl.sq.count, ex, ey, ez, bx, by, bz, g, q, m, dt, ext, hook);
+    }); }); }); });
+    WXA_LAUNCH_CHECK();
+    return WXA_OK;
 }
 
 }  // namespace wxa

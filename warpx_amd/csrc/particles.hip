@@ -4,6 +4,7 @@
 #include "deposit_body.hpp"
 #include <complex>
 
+#include "dispatch.hpp"
 #include "gather_body.hpp"
 #include "push_sort.hpp"
 #include "workspace.hpp"
@@ -284,6 +285,20 @@ static inline wxa_particle_view tail_view(const wxa_particle_view& p, int64_t fi
     return t;
 }
 
+// p as the LDS-tile kernels and the global-memory kernels share it: `head`, the particles of the last cell sort (empty
+// without a valid one: sorted_tiles_available), on the tiles, and `rest`, those appended since (arrivals from the
+// neighbouring bricks; everything without a valid sort), which start `first` particles into p
+struct HeadAndRest {
+    wxa_particle_view head, rest;
+    int64_t first;
+};
+static inline HeadAndRest split_at_sort(const wxa_workspace* ws, const wxa_particle_view& p) {
+    const int64_t first = sorted_tiles_available(ws, &p) ? ws->sorted_np : 0;
+    HeadAndRest s{p, tail_view(p, first), first};
+    s.head.np = first;
+    return s;
+}
+
 // ---- laser antenna push (LaserParticleContainer.cpp:795-951, LaserProfileGaussian.cpp:104-161) -------------
 // Everything that does not depend on the particle is folded on the host into a complex prefactor
 // P = e_max exp(i phase) / D * exp(-(t - t_peak)^2 / tau^2) and the complex inverse waist 1 / (w^2 D),
@@ -553,26 +568,6 @@ pack_leavers_kernel(PV p, const int* __restrict__ list, long n, double* __restri
     }
 }
 
-template <int PUSHER, bool MOVE>
-static wxa_status launch_gather_push(const PV& pv, const wxa_field_view E[3], const wxa_field_view B[3],
-                                     const Geom& g, double q, double m, double dt, int order, int galerkin,
-                                     const ExtEB& ext, const PushSort& hook, hipStream_t st) {
-    const DevF ex = make_devf(E[0]), ey = make_devf(E[1]), ez = make_devf(E[2]);
-    const DevF bx = make_devf(B[0]), by = make_devf(B[1]), bz = make_devf(B[2]);
-    const dim3 grid(blocks_for(pv.np)), block(256);
-#define WXA_GP(O, G)                                                                              \
-    hipLaunchKernelGGL((gather_push_kernel<O, G, PUSHER, MOVE>), grid, block, 0, st, pv, ex, ey, ez, bx, by, \
-                       bz, g, q, m, dt, ext, hook)
-    if (galerkin) {
-        if (order == 1) WXA_GP(1, 1); else if (order == 2) WXA_GP(2, 1); else if (order == 3) WXA_GP(3, 1); else WXA_GP(4, 1);
-    } else {
-        if (order == 1) WXA_GP(1, 0); else if (order == 2) WXA_GP(2, 0); else if (order == 3) WXA_GP(3, 0); else WXA_GP(4, 0);
-    }
-#undef WXA_GP
-    WXA_LAUNCH_CHECK();
-    return WXA_OK;
-}
-
 // per-particle external fields of the push that follows (none unless the workspace carries a lens)
 static wxa_status evaluate_particle_fields(const wxa_particle_view* p, wxa_workspace* ws, hipStream_t st) {
     if (!ws) return WXA_OK;
@@ -617,20 +612,17 @@ static wxa_status gather_push_global(const wxa_particle_view& rest, const wxa_fi
                                      int pusher, int move, const ExtEB& ext, const PushSort& hook, hipStream_t st) {
     const PV pv = make_pv(rest);
     const Geom g = make_geom(*geom);
-    if (pusher == WXA_PUSHER_BORIS) {
-        if (move) return launch_gather_push<WXA_PUSHER_BORIS, true>(pv, E, B, g, q, m, dt, order, galerkin, ext, hook, st);
-        return launch_gather_push<WXA_PUSHER_BORIS, false>(pv, E, B, g, q, m, dt, order, galerkin, ext, hook, st);
-    }
-    if (pusher == WXA_PUSHER_VAY) {
-        if (move) return launch_gather_push<WXA_PUSHER_VAY, true>(pv, E, B, g, q, m, dt, order, galerkin, ext, hook, st);
-        return launch_gather_push<WXA_PUSHER_VAY, false>(pv, E, B, g, q, m, dt, order, galerkin, ext, hook, st);
-    }
-    if (pusher == WXA_PUSHER_HC) {
-        if (move) return launch_gather_push<WXA_PUSHER_HC, true>(pv, E, B, g, q, m, dt, order, galerkin, ext, hook, st);
-        return launch_gather_push<WXA_PUSHER_HC, false>(pv, E, B, g, q, m, dt, order, galerkin, ext, hook, st);
-    }
-    if (move) return launch_gather_push<WXA_PUSHER_BORIS_RR, true>(pv, E, B, g, q, m, dt, order, galerkin, ext, hook, st);
-    return launch_gather_push<WXA_PUSHER_BORIS_RR, false>(pv, E, B, g, q, m, dt, order, galerkin, ext, hook, st);
+    const DevF ex = make_devf(E[0]), ey = make_devf(E[1]), ez = make_devf(E[2]);
+    const DevF bx = make_devf(B[0]), by = make_devf(B[1]), bz = make_devf(B[2]);
+    with_int<WXA_PUSHER_BORIS, WXA_PUSHER_VAY, WXA_PUSHER_HC, WXA_PUSHER_BORIS_RR>(pusher, [&](auto pu) {
+    with_int<1, 0>(move != 0, [&](auto mv) {
+    with_int<1, 2, 3, 4>(order, [&](auto o) {
+    with_int<1, 0>(galerkin, [&](auto gk) {
+        hipLaunchKernelGGL((gather_push_kernel<decltype(o)::value, decltype(gk)::value, decltype(pu)::value, decltype(mv)::value != 0>),
+                           dim3(blocks_for(pv.np)), dim3(256), 0, st, pv, ex, ey, ez, bx, by, bz, g, q, m, dt, ext, hook);
+    }); }); }); });
+    WXA_LAUNCH_CHECK();
+    return WXA_OK;
 }
 
 wxa_status wxa_gather_push_ws(const wxa_particle_view* p, const wxa_field_view E[3], const wxa_field_view B[3],
@@ -640,23 +632,16 @@ wxa_status wxa_gather_push_ws(const wxa_particle_view* p, const wxa_field_view E
     if (rc != WXA_OK) return rc;
     if (p->np == 0) return WXA_OK;
     if ((rc = evaluate_particle_fields(p, ws, (hipStream_t)stream)) != WXA_OK) return rc;
-    wxa_particle_view rest = *p;
-    int64_t first = 0;
-    if (gather_tile_available(ws, p)) {   // orders 1 .. 4 (4 since round 6: a tile of 13^3 / 14^3 staged points)
-        // sorted part on the LDS tiles; particles appended since the sort (arrivals from the
-        // neighbouring bricks) take the global-memory kernel below
-        wxa_particle_view head = *p;
-        head.np = ws->sorted_np;
-        if (head.np > 0 &&
-            (rc = gather_push_tiled(&head, E, B, geom, q, m, dt, order, galerkin, pusher, move != 0, ws,
-                                    (hipStream_t)stream)) != WXA_OK)
-            return rc;
-        rest = tail_view(*p, ws->sorted_np);
-        first = ws->sorted_np;
-        if (rest.np == 0) return WXA_OK;
-    }
-    return gather_push_global(rest, E, B, geom, q, m, dt, order, galerkin, pusher, move, ext_of(ws, first),
-                              make_push_sort(ws, first, move != 0), (hipStream_t)stream);
+    // sorted part on the LDS tiles (orders 1 .. 4; 4 since round 6: a tile of 13^3 / 14^3 staged points); particles
+    // appended since the sort (arrivals from the neighbouring bricks) take the global-memory kernel below
+    const HeadAndRest s = split_at_sort(ws, *p);
+    if (s.head.np > 0 &&
+        (rc = gather_push_tiled(&s.head, E, B, geom, q, m, dt, order, galerkin, pusher, move != 0, 0, ws,
+                                (hipStream_t)stream)) != WXA_OK)
+        return rc;
+    if (s.rest.np == 0) return WXA_OK;
+    return gather_push_global(s.rest, E, B, geom, q, m, dt, order, galerkin, pusher, move, ext_of(ws, s.first),
+                              make_push_sort(ws, s.first, move != 0), (hipStream_t)stream);
 }
 
 wxa_status wxa_gather_push_part(const wxa_particle_view* p, const wxa_field_view E[3], const wxa_field_view B[3],
@@ -667,22 +652,14 @@ wxa_status wxa_gather_push_part(const wxa_particle_view* p, const wxa_field_view
     WXA_REQUIRE(part == WXA_PART_INTERIOR || part == WXA_PART_REST, "part must be WXA_PART_INTERIOR or WXA_PART_REST");
     if (p->np == 0) return WXA_OK;
     if ((rc = evaluate_particle_fields(p, ws, (hipStream_t)stream)) != WXA_OK) return rc;
-    if (!gather_tile_available(ws, p)) {   // no tiles: the interior part is empty, the rest is everything
-        if (part == WXA_PART_INTERIOR) return WXA_OK;
-        return gather_push_global(*p, E, B, geom, q, m, dt, order, galerkin, pusher, 1, ext_of(ws), make_push_sort(ws, 0, true),
-                                  (hipStream_t)stream);
-    }
-    wxa_particle_view head = *p;
-    head.np = ws->sorted_np;
-    if (head.np > 0 &&
-        (rc = gather_push_tiled_part(&head, E, B, geom, q, m, dt, order, galerkin, pusher, part, ws,
-                                     (hipStream_t)stream)) != WXA_OK)
+    const HeadAndRest s = split_at_sort(ws, *p);   // no tiles: the interior part is empty, the rest is everything
+    if (s.head.np > 0 &&
+        (rc = gather_push_tiled(&s.head, E, B, geom, q, m, dt, order, galerkin, pusher, true, part, ws,
+                                (hipStream_t)stream)) != WXA_OK)
         return rc;
-    if (part == WXA_PART_INTERIOR) return WXA_OK;
-    const wxa_particle_view rest = tail_view(*p, ws->sorted_np);   // arrivals since the sort may sit anywhere
-    if (rest.np == 0) return WXA_OK;
-    return gather_push_global(rest, E, B, geom, q, m, dt, order, galerkin, pusher, 1, ext_of(ws, ws->sorted_np),
-                              make_push_sort(ws, ws->sorted_np, true), (hipStream_t)stream);
+    if (part == WXA_PART_INTERIOR || s.rest.np == 0) return WXA_OK;   // arrivals since the sort may sit anywhere
+    return gather_push_global(s.rest, E, B, geom, q, m, dt, order, galerkin, pusher, 1, ext_of(ws, s.first),
+                              make_push_sort(ws, s.first, true), (hipStream_t)stream);
 }
 
 wxa_status wxa_gather_push(const wxa_particle_view* p, const wxa_field_view E[3], const wxa_field_view B[3],
@@ -711,34 +688,25 @@ wxa_status wxa_deposit_current(const wxa_particle_view* p, const wxa_field_view 
         return WXA_ERR_UNSUPPORTED;
     }
     if (p->np == 0) return WXA_OK;
-    wxa_particle_view rest = *p;
-    if (ws && deposit_tile_available(ws, p)) {   // orders 1 .. 4 (4 since round 6: the tile's points are exactly the quartic stencil's reach)
-        wxa_particle_view head = *p;
-        head.np = ws->sorted_np;
-        wxa_status rc;
-        if (head.np > 0 && (rc = deposit_current_tiled(&head, J, geom, q, dt, relative_time, order, algo, ws,
-                                                       (hipStream_t)stream)) != WXA_OK)
-            return rc;
-        rest = tail_view(*p, ws->sorted_np);   // arrivals since the sort: global atomics
-        if (rest.np == 0) return WXA_OK;
-    }
-    const PV pv = make_pv(rest);
+    hipStream_t st = (hipStream_t)stream;
+    // sorted part on the LDS tiles (orders 1 .. 4; 4 since round 6: the tile's points are exactly the quartic stencil's
+    // reach); arrivals since the sort: global atomics
+    const HeadAndRest s = split_at_sort(ws, *p);
+    wxa_status rc;
+    if (s.head.np > 0 && (rc = deposit_current_tiled(&s.head, J, geom, q, dt, relative_time, order, algo, ws, st)) != WXA_OK)
+        return rc;
+    if (s.rest.np == 0) return WXA_OK;
+    const PV pv = make_pv(s.rest);
     const Geom g = make_geom(*geom);
     const DevF jx = make_devf(J[0]), jy = make_devf(J[1]), jz = make_devf(J[2]);
     const dim3 grid(blocks_for(pv.np)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (algo == WXA_DEPOSIT_ESIRKEPOV) {
-        const EsirkepovStep es = make_esirkepov_step(g, dt, relative_time);
-        if (order == 1) hipLaunchKernelGGL(deposit_esirkepov_global_kernel<1>, grid, block, 0, st, pv, jx, jy, jz, g, q, es);
-        else if (order == 2) hipLaunchKernelGGL(deposit_esirkepov_global_kernel<2>, grid, block, 0, st, pv, jx, jy, jz, g, q, es);
-        else if (order == 3) hipLaunchKernelGGL(deposit_esirkepov_global_kernel<3>, grid, block, 0, st, pv, jx, jy, jz, g, q, es);
-        else hipLaunchKernelGGL(deposit_esirkepov_global_kernel<4>, grid, block, 0, st, pv, jx, jy, jz, g, q, es);
-    } else {
-        if (order == 1) hipLaunchKernelGGL(deposit_direct_global_kernel<1>, grid, block, 0, st, pv, jx, jy, jz, g, q, relative_time);
-        else if (order == 2) hipLaunchKernelGGL(deposit_direct_global_kernel<2>, grid, block, 0, st, pv, jx, jy, jz, g, q, relative_time);
-        else if (order == 3) hipLaunchKernelGGL(deposit_direct_global_kernel<3>, grid, block, 0, st, pv, jx, jy, jz, g, q, relative_time);
-        else hipLaunchKernelGGL(deposit_direct_global_kernel<4>, grid, block, 0, st, pv, jx, jy, jz, g, q, relative_time);
-    }
+    with_int<1, 2, 3, 4>(order, [&](auto o) {
+        constexpr int O = decltype(o)::value;
+        if (algo == WXA_DEPOSIT_ESIRKEPOV)
+            hipLaunchKernelGGL(deposit_esirkepov_global_kernel<O>, grid, block, 0, st, pv, jx, jy, jz, g, q,
+                               make_esirkepov_step(g, dt, relative_time));
+        else hipLaunchKernelGGL(deposit_direct_global_kernel<O>, grid, block, 0, st, pv, jx, jy, jz, g, q, relative_time);
+    });
     WXA_LAUNCH_CHECK();
     return WXA_OK;
 }
@@ -752,12 +720,10 @@ wxa_status wxa_deposit_charge(const wxa_particle_view* p, const wxa_field_view* 
     const PV pv = make_pv(*p);
     const Geom g = make_geom(*geom);
     const DevF r = make_devf(*rho);
-    const dim3 grid(blocks_for(pv.np)), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (order == 1) hipLaunchKernelGGL(deposit_charge_kernel<1>, grid, block, 0, st, pv, r, rho->stag[0], rho->stag[1], rho->stag[2], g, q);
-    else if (order == 2) hipLaunchKernelGGL(deposit_charge_kernel<2>, grid, block, 0, st, pv, r, rho->stag[0], rho->stag[1], rho->stag[2], g, q);
-    else if (order == 3) hipLaunchKernelGGL(deposit_charge_kernel<3>, grid, block, 0, st, pv, r, rho->stag[0], rho->stag[1], rho->stag[2], g, q);
-    else hipLaunchKernelGGL(deposit_charge_kernel<4>, grid, block, 0, st, pv, r, rho->stag[0], rho->stag[1], rho->stag[2], g, q);
+    with_int<1, 2, 3, 4>(order, [&](auto o) {
+        hipLaunchKernelGGL(deposit_charge_kernel<decltype(o)::value>, dim3(blocks_for(pv.np)), dim3(256), 0, (hipStream_t)stream, pv,
+                           r, rho->stag[0], rho->stag[1], rho->stag[2], g, q);
+    });
     WXA_LAUNCH_CHECK();
     return WXA_OK;
 }

@@ -126,18 +126,17 @@ inline ExtLens lens_of(const wxa_workspace* ws) {
     L.tab = (const double*)ws->lens_tab.p;
     return L;
 }
+// the LDS-tile kernels can take p: its first ws->sorted_np particles are those of the last cell sort
+inline bool sorted_tiles_available(const wxa_workspace* ws, const wxa_particle_view* p) {
+    return ws && ws->sorted_valid && ws->sorted_x == p->x && ws->sorted_np <= p->np;
+}
 // LDS-tile deposition (deposit_tile.hip)
-bool deposit_tile_available(const wxa_workspace* ws, const wxa_particle_view* p);
 wxa_status deposit_current_tiled(const wxa_particle_view* p, const wxa_field_view J[3],
                                  const wxa_grid_geom* geom, double q, double dt, double relative_time,
                                  int order, int algo, wxa_workspace* ws, hipStream_t stream);
-// LDS-tile gather + push (gather_tile.hip)
-bool gather_tile_available(const wxa_workspace* ws, const wxa_particle_view* p);
+// LDS-tile gather + push (gather_tile.hip); part: 0 every tile, or WXA_PART_INTERIOR / WXA_PART_REST of a PushPX
 wxa_status gather_push_tiled(const wxa_particle_view* p, const wxa_field_view E[3], const wxa_field_view B[3],
                              const wxa_grid_geom* geom, double q, double m, double dt, int order, int galerkin,
-                             int pusher, bool move, wxa_workspace* ws, hipStream_t stream);
-wxa_status gather_push_tiled_part(const wxa_particle_view* p, const wxa_field_view E[3], const wxa_field_view B[3],
-                                  const wxa_grid_geom* geom, double q, double m, double dt, int order, int galerkin,
-                                  int pusher, int part, wxa_workspace* ws, hipStream_t stream);
+                             int pusher, bool move, int part, wxa_workspace* ws, hipStream_t stream);
 }  // namespace wxa
 #endif
