@@ -26,7 +26,7 @@ def main():
                 return int(m.group(1)) if m else None
             dem = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip()
             dem = re.sub(r"\(.*", "", dem).replace("void ", "").replace("wxa::", "")
-            rows.append((name, dem, g("VGPRs"), g("AGPRs"), g("SGPRs"), g(r"ScratchSize \[bytes/lane\]"),
+            rows.append((name, dem, g("VGPRs"), g("AGPRs"), g("SGPRs"), g("SGPRs Spill"), g(r"ScratchSize \[bytes/lane\]"),
                          g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")))
     seen, out = set(), []
     for r in rows:
@@ -36,9 +36,11 @@ def main():
     w = sys.stdout.write
     w("# Static resource usage of every kernel\n\n`hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage` "
       "(the product's flags; scripts/static_kernel_resources.py), taken in the build\ncontainer: compiler output, not a "
-      "measurement.  Scratch = spilled bytes per lane, occupancy = waves per SIMD the register and LDS budgets allow.\n"
-      "Template arguments: gather `<order, galerkin, pusher, move, part>`, deposit `<order, algo, ...>`.\n\n"
-      "| file | kernel | VGPRs | AGPRs | SGPRs | scratch B/lane | waves/SIMD | LDS B/workgroup |\n|---|---|---|---|---|---|---|---|\n")
+      "measurement.  Scratch = spilled bytes per lane, occupancy = waves per SIMD the register and LDS budgets allow;\n"
+      "sgpr_spill = SGPRs the compiler parks in VGPR lanes (a wave has 102): each reload is a v_readlane_b32, a vector-ALU\n"
+      "instruction -- tests/test_sgpr_spills_cpu.py keeps them out of the loops of the headline kernels.\n"
+      "Template arguments: gather `<order, galerkin, pusher, move, part, sort mode>`, deposit `<order, algo, ...>`.\n\n"
+      "| file | kernel | VGPRs | AGPRs | SGPRs | sgpr_spill | scratch B/lane | waves/SIMD | LDS B/workgroup |\n|---|---|---|---|---|---|---|---|---|\n")
     for r in out:
         w("| " + " | ".join(str(x) for x in r) + " |\n")
 

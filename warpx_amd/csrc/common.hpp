@@ -15,6 +15,25 @@
 #define WXA_OPAQUE_I32(v) asm volatile("" : "+v"(v))
 #endif
 
+// A kernel's FIRST parameter (a struct of type T) read where it is used instead of being held in SGPRs from the kernel's
+// entry on: a pointer to it in the kernel-argument segment (constant address space: uniform fields come as scalar loads,
+// which the scalar cache serves), and a barrier that keeps the compiler from hoisting those loads out of a loop -- put
+// in the loop's body on a copy of the pointer.  The kernel does not name the parameter anywhere else.
+// tests/hipcpu defines WXA_LATE_KERNARG as the parameter's address.
+// On the device the macro cannot look at the parameter: it is the segment's offset 0 whatever `first_param` names.  So
+// the struct's first member is `late_tag`, which the host leaves at WXA_LATE_TAG, and the kernel starts with
+// WXA_LATE_CHECK(pointer): a kernel whose parameter list was reordered stops there instead of computing with whatever
+// lies at offset 0 (the CPU execution model, which takes the parameter's address, would not notice).
+#ifndef WXA_LATE_KERNARG
+#define WXA_LATE_KERNARG(T, first_param) ((const __attribute__((address_space(4))) T*)__builtin_amdgcn_kernarg_segment_ptr())
+#define WXA_OPAQUE_UNIFORM_PTR(p) asm volatile("" : "+s"(p))
+#else
+#define WXA_OPAQUE_UNIFORM_PTR(p) ((void)0)
+#endif
+
+constexpr unsigned long long WXA_LATE_TAG = 0x57584131004c4154ull;
+#define WXA_LATE_CHECK(p) do { if ((p)->late_tag != WXA_LATE_TAG) __builtin_trap(); } while (0)
+
 // Register budget of a kernel as waves per SIMD (512 VGPRs per lane and SIMD: 4 -> 128, 3 -> 168 VGPRs)
 #ifndef WXA_WAVES_PER_SIMD
 #define WXA_WAVES_PER_SIMD(n) __attribute__((amdgpu_waves_per_eu(n, n)))

@@ -74,17 +74,17 @@ struct LdsField {
     static constexpr long js = N, ks = N * N;
 };
 
-template <int PUSHER, bool MOVE>
+template <int PUSHER, bool MOVE, int MODE, class E, class H>
 __device__ __forceinline__ void push_and_store(const PV& p, int ip, double xp, double yp, double zp, double ux, double uy,
                                                double uz, double Exp, double Eyp, double Ezp, double Bxp, double Byp,
-                                               double Bzp, double q, double m, double dt, const ExtEB& ext,
-                                               const PushSort& hook,
+                                               double Bzp, double q, double m, double dt, const E* ext,
+                                               const H* hook,
                                                int* lds_hist = nullptr, const long my_tile = -1) {   // push_sort_tail
     add_external_fields(ext, ip, Exp, Eyp, Ezp, Bxp, Byp, Bzp);
     push_momentum<PUSHER>(ux, uy, uz, Exp, Eyp, Ezp, Bxp, Byp, Bzp, q, m, dt);
     if constexpr (MOVE) update_position(xp, yp, zp, ux, uy, uz, dt);
-    if constexpr (MOVE) {   // the cell sort folded into the push (push_sort.hpp): keyed, or written to the sorted tile
-        if (!push_sort_tail(hook, p, ip, xp, yp, zp, ux, uy, uz, lds_hist, my_tile)) return;
+    if constexpr (MOVE && MODE != 0) {   // the cell sort folded into the push (push_sort.hpp): keyed, or written to the sorted tile
+        if (!push_sort_tail<MODE>(hook, p, ip, xp, yp, zp, ux, uy, uz, lds_hist, my_tile)) return;
     }
     p.ux[ip] = ux; p.uy[ip] = uy; p.uz[ip] = uz;
     if constexpr (MOVE) { p.x[ip] = xp; p.y[ip] = yp; p.z[ip] = zp; }
@@ -96,17 +96,44 @@ __device__ __forceinline__ void push_and_store(const PV& p, int ip, double xp, d
 // point, even as stragglers: a particle is at most a few cells from the tile it was sorted into); 2 = only
 // the tiles that do.  1 and 2 let the guard exchange of E and B travel behind the interior tiles
 // (wxa_gather_push_part); the default path instantiates PART = 0 and is unchanged by them.
-template <int O, int G, int PUSHER, bool MOVE, int PART = 0>
+// MODE: 0, a plain push, or PUSH_SORT_RUNTIME: the cell sort is folded into this push (MOVE only) and the hook says what is
+// armed (COUNT, SCATTER or both) -- one more instantiation per kernel, not three: with the hook read late a mode known at
+// compile time bought no register and no instruction worth 200 more kernels.
+// A wave has 102 SGPRs and the particle loop needs most of them for the particle arrays, the geometry and its own
+// bookkeeping.  What a trip uses once or rarely -- the external fields, the straggler queue, the hook of the folded sort
+// (push_sort.hpp; a plain push has none) -- is the kernel's first argument and is read from the kernel-argument segment
+// where it is used (WXA_LATE_KERNARG, common.hpp) instead of being spilled to VGPR lanes and fetched back by
+// v_readlane_b32 in every trip.
+template <bool SORT>
+struct TileLateArgs {
+    unsigned long long late_tag = WXA_LATE_TAG;
+    ExtEB ext;
+    StragglerQueue sq;
+    PushSort hook;
+};
+template <>
+struct TileLateArgs<false> {
+    unsigned long long late_tag = WXA_LATE_TAG;
+    ExtEB ext;
+    StragglerQueue sq;
+};
+template <int O, int G, int PUSHER, bool MOVE, int PART = 0, int MODE = 0>
 __global__ void __launch_bounds__(GT_THREADS) WXA_WAVES_PER_SIMD(O <= 3 ? 4 : 2)   // what the staged tile lets a CU hold
-gather_push_tile_kernel(PV p, const int* __restrict__ offsets, DevF Ex, DevF Ey, DevF Ez, DevF Bx, DevF By,
-                        DevF Bz, Geom g, TileGeom tg, double q, double m, double dt, StragglerQueue sq, ExtEB ext,
-                        PushSort hook, HeavyUnits hu) {
+gather_push_tile_kernel(TileLateArgs<MODE != 0> late_args, PV p, const int* __restrict__ offsets, DevF Ex, DevF Ey, DevF Ez,
+                        DevF Bx, DevF By, DevF Bz, Geom g, TileGeom tg, double q, double m, double dt, HeavyUnits hu) {
+    static_assert(MOVE || MODE == 0, "the sort is folded into pushes that move the particles");
+    static_assert(MODE == 0 || MODE == PUSH_SORT_RUNTIME, "a plain push, or the mode the hook names");
+    const auto late = WXA_LATE_KERNARG(TileLateArgs<MODE != 0>, late_args);
+    WXA_LATE_CHECK(late);
     constexpr int N = GatherTileDims<G, O>::N;
     constexpr int NPTS = GatherTileDims<G, O>::NPTS;
     constexpr bool SPLIT = G == 0 && O <= 3;   // per-component stage (SplitTile)
     __shared__ double F[SPLIT ? SplitTile::total() : 6 * NPTS];
     const long ntiles = (long)tg.nt[0] * tg.nt[1] * tg.nt[2];
-    if (blockIdx.x == 0 && threadIdx.x == 0 && sq.next) *sq.next = 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        unsigned* const next = late->sq.next;
+        if (next) *next = 0u;
+    }
     // a tile with far more particles than the others is shared by several workgroups, each with a part of its particles
     // (heavy_tiles.hpp)
     long tile;
@@ -151,7 +178,8 @@ gather_push_tile_kernel(PV p, const int* __restrict__ offsets, DevF Ex, DevF Ey,
     static_assert(GT_THREADS == PUSH_SORT_TILE_CELLS, "one lane per cell of the tile");
     __shared__ int lhist[MOVE ? PUSH_SORT_TILE_CELLS : 1];
     // (COUNT alone or together with SCATTER: the keys are those of the tile being read either way)
-    const bool count_local = MOVE && (hook.mode & PUSH_SORT_COUNT) != 0 && unit_u == 0;   // uniform (a shared tile: unit 0's histogram)
+    bool count_local = false;
+    if constexpr (MODE != 0) count_local = (late->hook.mode & PUSH_SORT_COUNT) != 0 && unit_u == 0;   // uniform (a shared tile: unit 0's histogram)
     if constexpr (MOVE) {
         if (count_local) lhist[tid] = 0;   // visible after the staging barrier below
     }
@@ -159,10 +187,10 @@ gather_push_tile_kernel(PV p, const int* __restrict__ offsets, DevF Ex, DevF Ey,
     __shared__ int slist[SCAP];
     __shared__ int sn, sbase;
     if (tid == 0) sn = 0;   // visible after the staging barrier below
-    auto push_straggler = [&](const int i) {
+    auto push_straggler = [&](const int i, const auto* la) {
         const int n = atomicAdd(&sn, 1);
         if (n < SCAP) slist[n] = i;
-        else sq.push(i);
+        else la->sq.idx[atomicAdd(la->sq.count, 1u)] = i;   // StragglerQueue::push
     };
     constexpr int WAVES = GT_THREADS / 64;
     __shared__ int next_chunk;
@@ -244,6 +272,8 @@ gather_push_tile_kernel(PV p, const int* __restrict__ offsets, DevF Ex, DevF Ey,
         cb_next = start + 64 * __builtin_amdgcn_readfirstlane(__shfl(claimed, 0));
     };
     for (; ip < end; advance()) {
+        auto la = late;
+        WXA_OPAQUE_UNIFORM_PTR(la);   // what this trip reads of the late arguments is loaded in this trip, not held across the loop
         GPROF_CLOCK(prof_a);
         double xp = nxt[0], yp = nxt[1], zp = nxt[2], ux0, uy0, uz0;
         asm volatile("" ::: "memory");
@@ -267,7 +297,7 @@ gather_push_tile_kernel(PV p, const int* __restrict__ offsets, DevF Ex, DevF Ey,
             staged = staged && s.jn - o0 >= 1 && s.kn - o1 >= 1 && s.ln - o2 >= 1;
         }
         if (!staged) {
-            push_straggler(ip);   // stencil leaves the staged tile: handled by gather_push_stragglers_kernel
+            push_straggler(ip, la);   // stencil leaves the staged tile: handled by gather_push_stragglers_kernel
             continue;
         }
         const int jn = s.jn - o0, jc = s.jc - o0, kn = s.kn - o1, kc = s.kc - o1, ln = s.ln - o2, lc = s.lc - o2;
@@ -311,8 +341,12 @@ gather_push_tile_kernel(PV p, const int* __restrict__ offsets, DevF Ex, DevF Ey,
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(prof_e));
 #endif
         GPROF_CLOCK(prof_c);
-        push_and_store<PUSHER, MOVE>(p, ip, xp, yp, zp, ux0, uy0, uz0, Exp, Eyp, Ezp, Bxp, Byp, Bzp, q, m, dt, ext, hook,
-                                     count_local ? lhist : nullptr, tile);
+        if constexpr (MODE != 0)
+            push_and_store<PUSHER, MOVE, MODE>(p, ip, xp, yp, zp, ux0, uy0, uz0, Exp, Eyp, Ezp, Bxp, Byp, Bzp, q, m, dt, &la->ext,
+                                               &la->hook, count_local ? lhist : nullptr, tile);
+        else
+            push_and_store<PUSHER, MOVE, 0>(p, ip, xp, yp, zp, ux0, uy0, uz0, Exp, Eyp, Ezp, Bxp, Byp, Bzp, q, m, dt, &la->ext,
+                                            (const PushSort*)nullptr);
 #ifdef WXA_GATHER_PROFILE
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         GPROF_CLOCK(prof_d);
@@ -326,14 +360,15 @@ gather_push_tile_kernel(PV p, const int* __restrict__ offsets, DevF Ex, DevF Ey,
     {
         __syncthreads();
         const int n = min(sn, SCAP);
-        if (tid == 0 && n > 0) sbase = (int)atomicAdd(sq.count, (unsigned)n);
+        if (tid == 0 && n > 0) sbase = (int)atomicAdd(late->sq.count, (unsigned)n);
         __syncthreads();
-        for (int i = tid; i < n; i += GT_THREADS) sq.idx[sbase + i] = slist[i];
+        int* const sq_idx = late->sq.idx;
+        for (int i = tid; i < n; i += GT_THREADS) sq_idx[sbase + i] = slist[i];
     }
     if constexpr (MOVE) {
         if (count_local) {
             __syncthreads();
-            push_sort_tile_finish(hook, lhist, tile, tid);
+            if constexpr (MODE != 0) push_sort_tile_finish(&late->hook, lhist, tile, tid);
         }
     }
 }
@@ -351,8 +386,8 @@ gather_push_stragglers_kernel(PV p, const int* __restrict__ idx, const unsigned*
         gather_shapes<O, G>(xp, yp, zp, g, s);
         double Exp, Eyp, Ezp, Bxp, Byp, Bzp;
         gather_global<O, G>(s, Ex, Ey, Ez, Bx, By, Bz, Exp, Eyp, Ezp, Bxp, Byp, Bzp);
-        push_and_store<PUSHER, MOVE>(p, ip, xp, yp, zp, p.ux[ip], p.uy[ip], p.uz[ip], Exp, Eyp, Ezp, Bxp, Byp, Bzp, q, m, dt,
-                                     ext, hook);
+        push_and_store<PUSHER, MOVE, PUSH_SORT_RUNTIME>(p, ip, xp, yp, zp, p.ux[ip], p.uy[ip], p.uz[ip], Exp, Eyp, Ezp, Bxp,
+                                                        Byp, Bzp, q, m, dt, &ext, &hook);
     }
 }
 
@@ -370,7 +405,9 @@ wxa_status gather_push_tiled(const wxa_particle_view* p, const wxa_field_view E[
     const ExtEB ext = ext_of(ws);
     const PushSort hook = make_push_sort(ws, 0, move);
     // what is pushed where: 0 PushP on every tile; PushPX on 1 every tile, 2 the interior tiles, 3 the tiles on a face
-    // (the parts exist for PushPX alone: no <..., MOVE = false, PART != 0> kernels)
+    // (the parts and the sort modes exist for PushPX alone: no <..., MOVE = false, PART != 0 or MODE != 0> kernels;
+    // hook.mode is 0 when the push does not move the particles)
+    with_int<0, PUSH_SORT_RUNTIME>(hook.mode != 0 ? PUSH_SORT_RUNTIME : 0, [&](auto md) {
     with_int<0, 1, 2, 3>(move ? 1 + part : 0, [&](auto what) {
     with_int<WXA_PUSHER_BORIS, WXA_PUSHER_VAY, WXA_PUSHER_HC, WXA_PUSHER_BORIS_RR>(pusher, [&](auto pu) {
     with_int<1, 2, 3, 4>(order, [&](auto o) {
@@ -378,11 +415,16 @@ wxa_status gather_push_tiled(const wxa_particle_view* p, const wxa_field_view E[
         constexpr int O = decltype(o)::value, G = decltype(gk)::value, PUSHER = decltype(pu)::value;
         constexpr bool MOVE = decltype(what)::value != 0;
         constexpr int PART = MOVE ? decltype(what)::value - 1 : 0;
-        hipLaunchKernelGGL((gather_push_tile_kernel<O, G, PUSHER, MOVE, PART>), dim3(tl.groups), dim3(GT_THREADS), 0, st, pv,
-                           tl.offsets, ex, ey, ez, bx, by, bz, g, tl.tg, q, m, dt, tl.sq, ext, hook, tl.hu);
+        constexpr int MODE = MOVE ? decltype(md)::value : 0;
+        TileLateArgs<MODE != 0> late;
+        late.ext = ext;
+        late.sq = tl.sq;
+        if constexpr (MODE != 0) late.hook = hook;
+        hipLaunchKernelGGL((gather_push_tile_kernel<O, G, PUSHER, MOVE, PART, MODE>), dim3(tl.groups), dim3(GT_THREADS), 0, st,
+                           late, pv, tl.offsets, ex, ey, ez, bx, by, bz, g, tl.tg, q, m, dt, tl.hu);
         hipLaunchKernelGGL((gather_push_stragglers_kernel<O, G, PUSHER, MOVE>), dim3(WXA_STRAGGLER_BLOCKS), dim3(256), 0, st,
                            pv, tl.sq.idx, tl.sq.count, ex, ey, ez, bx, by, bz, g, q, m, dt, ext, hook);
-    }); }); }); });
+    }); }); }); }); });
     WXA_LAUNCH_CHECK();
     return WXA_OK;
 }

@@ -30,7 +30,7 @@ gather_push_kernel(PV p, DevF Ex, DevF Ey, DevF Ez, DevF Bx, DevF By, DevF Bz, G
     push_momentum<PUSHER>(ux, uy, uz, Exp, Eyp, Ezp, Bxp, Byp, Bzp, q, m, dt);
     if constexpr (MOVE) {
         update_position(xp, yp, zp, ux, uy, uz, dt);
-        if (!push_sort_tail(hook, p, ip, xp, yp, zp, ux, uy, uz)) return;   // written to the sorted tile instead
+        if (!push_sort_tail<PUSH_SORT_RUNTIME>(&hook, p, ip, xp, yp, zp, ux, uy, uz)) return;   // written to the sorted tile instead
         p.x[ip] = xp; p.y[ip] = yp; p.z[ip] = zp;
     }
     p.ux[ip] = ux; p.uy[ip] = uy; p.uz[ip] = uz;

@@ -261,18 +261,26 @@ struct ExtEB {
     double ex, ey, ez, bx, by, bz;
     ExtPerParticle pp;
 };
-__device__ __forceinline__ void add_external_fields(const ExtEB& ext, long ip, double& Ex, double& Ey, double& Ez, double& Bx,
+// (E: ExtEB, or ExtEB in the address space of kernel arguments that are read late -- WXA_LATE_KERNARG, common.hpp)
+template <class E>
+__device__ __forceinline__ void add_external_fields(const E* ext, long ip, double& Ex, double& Ey, double& Ez, double& Bx,
                                                     double& By, double& Bz) {
-    Ex += ext.ex; Ey += ext.ey; Ez += ext.ez; Bx += ext.bx; By += ext.by; Bz += ext.bz;
+    Ex += ext->ex; Ey += ext->ey; Ez += ext->ez; Bx += ext->bx; By += ext->by; Bz += ext->bz;
     // the gathered sums are complete here: without the pins the compiler sinks their tails past the branch below and the
     // register allocation of the 252-point gather falls apart (93 -> 247 VGPRs in the tile kernel)
     WXA_OPAQUE_F64(Ex); WXA_OPAQUE_F64(Ey); WXA_OPAQUE_F64(Ez); WXA_OPAQUE_F64(Bx); WXA_OPAQUE_F64(By); WXA_OPAQUE_F64(Bz);
-    if (ext.pp.fields) {   // uniform
-        Ex += ext.pp.fields[ip];
-        Ey += ext.pp.fields[ext.pp.stride + ip];
-        Bx += ext.pp.fields[2 * ext.pp.stride + ip];
-        By += ext.pp.fields[3 * ext.pp.stride + ip];
+    const double* const fields = ext->pp.fields;
+    if (fields) {   // uniform
+        const long stride = ext->pp.stride;
+        Ex += fields[ip];
+        Ey += fields[stride + ip];
+        Bx += fields[2 * stride + ip];
+        By += fields[3 * stride + ip];
     }
+}
+__device__ __forceinline__ void add_external_fields(const ExtEB& ext, long ip, double& Ex, double& Ey, double& Ez, double& Bx,
+                                                    double& By, double& Bz) {
+    add_external_fields(&ext, ip, Ex, Ey, Ez, Bx, By, Bz);
 }
 
 // GetExternalEBField::operator() (Source/Particles/Gather/GetExternalFields.H:137-189): the lens fields seen by a
