@@ -214,3 +214,131 @@ def test_push_sort_modes(product, case, parts, every_step, monkeypatch):
         assert seen["appended"] >= 1 and seen["retired"] >= 1, seen
     if case == "stale_sort":
         assert seen["straggler"] >= n0 // 20, seen
+
+
+def test_push_sort_protocol(product):
+    """The record of a COUNT through its life (include/warpx_amd.h, wxa_push_sort_begin): who it is pending for, what
+    drops it, every refused begin / end, and that a refused call arms nothing and drops nothing -- a correct
+    begin / push / end follows each one on the same workspace.  (16, 8, 8) cells: two tiles; 2 000 sorted particles and
+    50 appended behind them; order 1.  No tolerance: statuses, the pending flag, and one bit-for-bit comparison."""
+    import torch
+    ncell, order = (16, 8, 8), 1
+    n0, n_tail = 2000, 50
+    npart = n0 + n_tail
+    ng, _, _ = H.guard_depths(order)
+    Ed = H.clone_fields(H.random_fields(("Ex", "Ey", "Ez"), ncell, ng, 10, scale=1e11), DEV, True)
+    Bd = H.clone_fields(H.random_fields(("Bx", "By", "Bz"), ncell, ng, 11, scale=1e3), DEV, True)
+    g, dx = H.geom_for(ncell, ng)
+    dt = H.yee_dt(dx)
+    q, m = -plasma.Q_E, plasma.M_E
+    plo, phi, dinv = H.d3((-H.LX / 2,) * 3), H.d3((H.LX / 2,) * 3), H.d3(1.0 / dx)
+    lo, nc, wrap = (C.c_int32 * 3)(0, 0, 0), (C.c_int32 * 3)(*ncell), (C.c_int32 * 3)(1, 1, 1)
+    per = H.i3((1, 1, 1))
+    rows = [np.asarray(r) for r in H.random_particles(n0, ncell, 77, u_scale=30.0)]
+    tail = [np.asarray(r) for r in H.random_particles(n_tail, ncell, 78, u_scale=30.0)]
+    src = ParticleArrays.from_numpy(rows, DEV, np.arange(1, n0 + 1, dtype=np.int64))
+    cap = npart + 8
+    a, b, other = (ParticleArrays(cap, DEV, with_id=True) for _ in range(3))
+    ws = C.c_void_p()
+    product.workspace_create(C.byref(ws))
+    C_, S_ = _capi.PUSH_SORT_COUNT, _capi.PUSH_SORT_SCATTER
+    live, app = C.c_int64(), C.c_int64()
+
+    def view_of(pa, n):
+        v = pa.view
+        v.np = n
+        return v
+
+    def pending(pa, n=npart):
+        return product.push_sort_pending(ws, C.byref(view_of(pa, n)))
+
+    def sort_into_a():   # the classic sort: a's first n0 particles are src in cell order, the tail stays behind them
+        product.sort_particles_by_cell(C.byref(src.view), C.byref(view_of(a, n0)), plo, dinv, lo, nc, ws, None)
+        product.device_synchronize()
+
+    def begin(mode, p, d, np_=npart, nd=npart):
+        product.push_sort_begin(ws, mode, C.byref(view_of(p, np_)), C.byref(view_of(d, nd)), plo, dinv, lo, nc, wrap, 0, 0.0, None)
+
+    def push_and_end(p):
+        pv = view_of(p, npart)
+        product.gather_push_ws(C.byref(pv), field_triplet(Ed), field_triplet(Bd), C.byref(g), q, m, dt, order, 1,
+                               _capi.PUSHER_BORIS, 1, ws, None)
+        product.push_sort_end(ws, 0, C.byref(live), C.byref(app), None)
+        product.enforce_periodic(C.byref(pv), plo, phi, per, None)   # Redistribute: nobody drifts out of the guard cells
+        product.device_synchronize()
+
+    def take_record():   # a correct begin / push / end
+        begin(C_, a, b)
+        push_and_end(a)
+        assert pending(a) == 1
+
+    sort_into_a()
+    assert pending(a) == 0
+    for r in range(7):
+        a.data[r][n0:npart] = torch.from_numpy(tail[r]).to(DEV)
+    a.idcpu[n0:npart] = torch.from_numpy(np.arange(10 ** 5, 10 ** 5 + n_tail, dtype=np.int64)).to(DEV)
+
+    # who the record is pending for
+    take_record()
+    assert live.value == npart and app.value == 0
+    assert pending(other) == 0
+    assert pending(a, npart - 1) == 0 and pending(a, npart + 1) == 1
+    # what drops it
+    sort_into_a()
+    assert pending(a) == 0
+    take_record()
+    counts = (C.c_int64 * 3)()
+    product.partition_particles(C.byref(src.view), C.byref(view_of(b, n0)), 0, -H.LX / 4, H.LX / 4, counts, ws, None)
+    assert sum(counts) == n0 and pending(a) == 0
+    sort_into_a()   # (the partition dropped the tiles as well)
+
+    # begin while armed
+    begin(C_, a, b)
+    with pytest.raises(_capi.WxaError, match="without the wxa_push_sort_end"):
+        begin(C_, a, b)
+    push_and_end(a)   # still armed, by the first begin only
+    assert pending(a) == 1
+    take_record()
+    # end with nothing armed
+    with pytest.raises(_capi.WxaError, match="without wxa_push_sort_begin"):
+        product.push_sort_end(ws, 0, C.byref(live), C.byref(app), None)
+    take_record()
+    # SCATTER with no record
+    sort_into_a()
+    assert pending(a) == 0
+    with pytest.raises(_capi.WxaError, match="no record of a COUNT"):
+        begin(S_, a, b)
+    take_record()
+    # SCATTER with a record on other arrays, with dst aliasing p, with dst shorter than p: the record stays pending
+    for p, d, nd in ((other, b, npart), (a, a, npart), (a, b, npart - 1)):
+        with pytest.raises(_capi.WxaError):
+            begin(S_, p, d, nd=nd)
+        assert pending(a) == 1
+        with pytest.raises(_capi.WxaError, match="without wxa_push_sort_begin"):   # nothing was armed
+            product.push_sort_end(ws, 0, C.byref(live), C.byref(app), None)
+        take_record()
+    # the record is still good for what it is for: the sorting push into b, which takes the next record with it
+    begin(C_ | S_, a, b)
+    push_and_end(a)
+    assert live.value + app.value == npart
+    assert pending(b) == 1 and pending(a) == 0
+
+    # no sort recorded: nothing to count
+    ws2 = C.c_void_p()
+    product.workspace_create(C.byref(ws2))
+    with pytest.raises(_capi.WxaError, match="no sort recorded"):
+        product.sort_live_count(ws2, C.byref(live), None)
+    product.workspace_destroy(ws2)
+    # the sort in ws is of b: on another array the wrap through the sort is the plain pass, bit for bit
+    rng = np.random.default_rng(8)
+    for d in range(3):
+        other.data[d][:npart] = torch.from_numpy(H.LX * (1.5 * rng.random(npart) - 0.75)).to(DEV)
+    ref = ParticleArrays(cap, DEV, with_id=True)
+    ref.data.copy_(other.data)
+    product.enforce_periodic(C.byref(view_of(ref, npart)), plo, phi, per, None)
+    product.enforce_periodic_sorted(C.byref(view_of(other, npart)), plo, phi, per, ws, 0, None)
+    product.device_synchronize()
+    assert torch.equal(other.data[:3, :npart], ref.data[:3, :npart])
+    got = other.data[:3, :npart]
+    assert bool(((got >= -H.LX / 2) & (got < H.LX / 2)).all())
+    product.workspace_destroy(ws)

@@ -903,7 +903,7 @@ static wxa_status launch_rows(const wxa_particle_view* p, const wxa_field_view J
                                double q, double dt, double relative_time, wxa_workspace* ws, hipStream_t st) {
     TileLaunch tl;
     wxa_status rc;
-    if ((rc = plan_tile_launch(ws, (long)p->np, 0, ws->deposit_flips, st, tl)) != WXA_OK) return rc;   // words 0, 1 of ws->counters
+    if ((rc = plan_tile_launch(ws, (long)p->np, CW_DEPOSIT, ws->deposit_flips, st, tl)) != WXA_OK) return rc;
     const Geom g = make_geom(*geom);
     const DevF jx = make_devf(J[0]), jy = make_devf(J[1]), jz = make_devf(J[2]);
     const EsirkepovStep es = make_esirkepov_step(g, dt, relative_time);

@@ -397,7 +397,7 @@ wxa_status gather_push_tiled(const wxa_particle_view* p, const wxa_field_view E[
                              int pusher, bool move, int part, wxa_workspace* ws, hipStream_t st) {
     TileLaunch tl;
     wxa_status rc;
-    if ((rc = plan_tile_launch(ws, (long)p->np, 16, ws->gather_flips, st, tl)) != WXA_OK) return rc;   // words 16, 17 of ws->counters
+    if ((rc = plan_tile_launch(ws, (long)p->np, CW_GATHER, ws->gather_flips, st, tl)) != WXA_OK) return rc;
     const PV pv = make_pv(*p);
     const Geom g = make_geom(*geom);
     const DevF ex = make_devf(E[0]), ey = make_devf(E[1]), ez = make_devf(E[2]);

@@ -293,7 +293,7 @@ struct HeadAndRest {
     int64_t first;
 };
 static inline HeadAndRest split_at_sort(const wxa_workspace* ws, const wxa_particle_view& p) {
-    const int64_t first = sorted_tiles_available(ws, &p) ? ws->sorted_np : 0;
+    const int64_t first = sorted_tiles_available(ws, &p) ? ws->sorted.np : 0;
     HeadAndRest s{p, tail_view(p, first), first};
     s.head.np = first;
     return s;
@@ -600,6 +600,25 @@ static wxa_status check_gather_args(const wxa_particle_view* p, const wxa_field_
     return WXA_OK;
 }
 
+// out[i] = in[0] + ... + in[i - 1], i < n (hipCUB; its temporary storage is ws->scan_tmp)
+static wxa_status exclusive_scan(int* in, int* out, int n, wxa_workspace* ws, hipStream_t st) {
+    size_t tmp_bytes = 0;
+    WXA_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, in, out, n, st));
+    if (const wxa_status rc = ws->scan_tmp.reserve(tmp_bytes); rc != WXA_OK) return rc;
+    WXA_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(ws->scan_tmp.p, tmp_bytes, in, out, n, st));
+    return WXA_OK;
+}
+
+// the box of a periodic wrap; any: some direction is periodic (none: there is nothing to wrap)
+static wxa_status make_periodic_box(const double plo[3], const double phi[3], const int periodic[3], PeriodicBox& pb, bool& any) {
+    any = false;
+    for (int d = 0; d < 3; ++d) {
+        pb.plo[d] = plo[d]; pb.phi[d] = phi[d]; pb.on[d] = periodic[d] ? 1 : 0;
+        if (periodic[d]) { WXA_REQUIRE(phi[d] > plo[d], "empty domain"); any = true; }
+    }
+    return WXA_OK;
+}
+
 }  // namespace wxa
 
 using namespace wxa;
@@ -733,12 +752,9 @@ wxa_status wxa_enforce_periodic(const wxa_particle_view* p, const double plo[3],
     WXA_REQUIRE(pv_ok(p) && plo && phi && periodic, "bad argument");
     if (p->np == 0) return WXA_OK;
     PeriodicBox pb;
-    bool any = false;
-    for (int d = 0; d < 3; ++d) {
-        pb.plo[d] = plo[d]; pb.phi[d] = phi[d]; pb.on[d] = periodic[d] ? 1 : 0;
-        if (periodic[d]) { WXA_REQUIRE(phi[d] > plo[d], "empty domain"); any = true; }
-    }
-    if (!any) return WXA_OK;
+    bool any;
+    const wxa_status rc = make_periodic_box(plo, phi, periodic, pb, any);
+    if (rc != WXA_OK || !any) return rc;
     hipLaunchKernelGGL(enforce_periodic_kernel, dim3(blocks_for(p->np)), dim3(256), 0, (hipStream_t)stream, p->x,
                        p->y, p->z, (long)p->np, pb);
     WXA_LAUNCH_CHECK();
@@ -795,24 +811,19 @@ wxa_status wxa_enforce_periodic_sorted(const wxa_particle_view* p, const double 
                                        void* stream) {
     WXA_REQUIRE(pv_ok(p) && plo && phi && periodic, "bad argument");
     // no usable sort, or the drift since it may exceed a tile: the plain pass over everything
-    if (!ws || !ws->sorted_valid || ws->sorted_x != p->x || ws->sorted_np > p->np || steps_since_sort < 0 ||
-        steps_since_sort > WXA_TILE - 2)
+    if (!sorted_tiles_available(ws, p) || steps_since_sort < 0 || steps_since_sort > WXA_TILE - 2)
         return wxa_enforce_periodic(p, plo, phi, periodic, stream);
     if (p->np == 0) return WXA_OK;
     PeriodicBox pb;
-    bool any = false;
-    for (int d = 0; d < 3; ++d) {
-        pb.plo[d] = plo[d]; pb.phi[d] = phi[d]; pb.on[d] = periodic[d] ? 1 : 0;
-        if (periodic[d]) { WXA_REQUIRE(phi[d] > plo[d], "empty domain"); any = true; }
-    }
-    if (!any) return WXA_OK;
-    const int nt0 = (ws->sort_nc[0] + WXA_TILE - 1) / WXA_TILE, nt1 = (ws->sort_nc[1] + WXA_TILE - 1) / WXA_TILE,
-              nt2 = (ws->sort_nc[2] + WXA_TILE - 1) / WXA_TILE;
+    bool any;
+    const wxa_status rc = make_periodic_box(plo, phi, periodic, pb, any);
+    if (rc != WXA_OK || !any) return rc;
+    const SortRecord& so = ws->sorted;
+    const int nt0 = so.tiles(0), nt1 = so.tiles(1), nt2 = so.tiles(2);
     hipLaunchKernelGGL(enforce_periodic_tiles_kernel, dim3((unsigned)(nt0 * nt1 * nt2) * EPT_SPLIT), dim3(EPT_THREADS), 0, (hipStream_t)stream,
-                       p->x, p->y, p->z, (const int*)ws->offsets.p, nt0, nt1, nt2, ws->sort_nc[0], ws->sort_nc[1],
-                       ws->sort_nc[2], pb);
-    if (p->np > ws->sorted_np) {   // appended since the sort
-        const wxa_particle_view tail = tail_view(*p, ws->sorted_np);
+                       p->x, p->y, p->z, (const int*)ws->offsets.p, nt0, nt1, nt2, so.nc[0], so.nc[1], so.nc[2], pb);
+    if (p->np > so.np) {   // appended since the sort
+        const wxa_particle_view tail = tail_view(*p, so.np);
         hipLaunchKernelGGL(enforce_periodic_kernel, dim3(blocks_for(tail.np)), dim3(256), 0, (hipStream_t)stream,
                            tail.x, tail.y, tail.z, (long)tail.np, pb);
     }
@@ -827,12 +838,12 @@ wxa_status wxa_sort_particles_by_cell(const wxa_particle_view* src, const wxa_pa
     WXA_REQUIRE(src->np == dst->np, "src/dst particle counts differ");
     WXA_REQUIRE(src->x != dst->x, "sort is out of place");
     WXA_REQUIRE(ncell[0] > 0 && ncell[1] > 0 && ncell[2] > 0, "empty cell box");
-    const long ncells = (long)((ncell[0] + WXA_TILE - 1) / WXA_TILE) * ((ncell[1] + WXA_TILE - 1) / WXA_TILE) *
-                        ((ncell[2] + WXA_TILE - 1) / WXA_TILE) * (WXA_TILE * WXA_TILE * WXA_TILE);
+    const SortRecord sorted = SortRecord::of(dst->x, src->np, plo, dinv, cell_lo, ncell);   // (np: wxa_sort_live_count lowers it)
+    const long ncells = sorted.bins;
     WXA_REQUIRE(ncells > 0 && ncells < (1L << 31) - 2 && src->np < (1L << 31) - 2, "sizes exceed 32-bit sort keys");
     hipStream_t st = (hipStream_t)stream;
-    ws->sorted_valid = false;
-    ws->ps.pending = false;   // a record of wxa_push_sort_begin(COUNT) indexes the order this sort replaces
+    ws->sorted.valid = false;
+    ws->ps.pending.valid = false;   // a record of wxa_push_sort_begin(COUNT) indexes the order this sort replaces
     if (src->np == 0) return WXA_OK;
     wxa_status rc;
     if ((rc = ws->rank.reserve(sizeof(int) * src->np)) != WXA_OK) return rc;   // (no key array: the scatter works the keys out again)
@@ -842,22 +853,11 @@ wxa_status wxa_sort_particles_by_cell(const wxa_particle_view* src, const wxa_pa
     int* rank = (int*)ws->rank.p;
     int* hist = (int*)ws->hist.p; int* offsets = (int*)ws->offsets.p;
     WXA_HIP_CHECK(hipMemsetAsync(hist, 0, sizeof(int) * (ncells + 2), st));
-    SortGeom sg;
-    for (int d = 0; d < 3; ++d) {
-        // physical lower corner of the brick's cell box; cells are numbered from cell_lo
-        sg.plo[d] = plo[d];
-        sg.dinv[d] = dinv[d];
-        sg.nc[d] = ncell[d];
-    }
-    sg.retired_bin = (int)ncells;
-    (void)cell_lo;
+    const SortGeom sg = sort_geom_of(sorted);
     const PV s = make_pv(*src), d = make_pv(*dst);
     hipLaunchKernelGGL(sort_count_kernel, dim3(blocks_for(s.np)), dim3(256), 0, st, s.x, s.y, s.z, s.id, s.np, sg,
                        (int*)nullptr, rank, hist);
-    size_t tmp_bytes = 0;
-    WXA_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, hist, offsets, (int)(ncells + 2), st));
-    if ((rc = ws->scan_tmp.reserve(tmp_bytes)) != WXA_OK) return rc;
-    WXA_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(ws->scan_tmp.p, tmp_bytes, hist, offsets, (int)(ncells + 2), st));
+    if ((rc = exclusive_scan(hist, offsets, (int)(ncells + 2), ws, st)) != WXA_OK) return rc;
     // the scatter works the keys out again from the positions it loads (round 4) and stages a chunk's near-stayers in LDS
     // in destination order, so that it writes whole lines.  Window shapes timed at 256^3 x 8 ppc (Redistribute per step;
     // the plain scatter -- one lane per particle, 8-byte writes wherever they fall -- 1.47): 8 x 512 lanes + 512 margin
@@ -865,16 +865,7 @@ wxa_status wxa_sort_particles_by_cell(const wxa_particle_view* src, const wxa_pa
     hipLaunchKernelGGL((sort_scatter_window_kernel<8, 512, true>), dim3(blocks_for(s.np, SW_THREADS * 8)), dim3(SW_THREADS), 0,
                        st, s, d, (const int*)nullptr, rank, offsets, sg);
     WXA_LAUNCH_CHECK();
-    ws->sorted_valid = true;
-    ws->sorted_np = src->np;   // wxa_sort_live_count lowers it to the live count
-    ws->sorted_bins = ncells;
-    ws->sorted_x = dst->x;
-    for (int e = 0; e < 3; ++e) {
-        ws->sort_nc[e] = ncell[e];
-        ws->sort_cell_lo[e] = cell_lo[e];
-        ws->sort_plo[e] = plo[e];
-        ws->sort_dinv[e] = dinv[e];
-    }
+    ws->sorted = sorted;
     return WXA_OK;
 }
 
@@ -886,8 +877,8 @@ wxa_status wxa_partition_particles(const wxa_particle_view* src, const wxa_parti
     WXA_REQUIRE(src->np < (1L << 31) - 2, "tile too large for 32-bit scan");
     hipStream_t st = (hipStream_t)stream;
     counts[0] = counts[1] = counts[2] = 0;
-    ws->sorted_valid = false;
-    ws->ps.pending = false;
+    ws->sorted.valid = false;
+    ws->ps.pending.valid = false;
     if (src->np == 0) return WXA_OK;
     wxa_status rc;
     if ((rc = ws->cell.reserve(sizeof(int) * (src->np + 1))) != WXA_OK) return rc;
@@ -899,10 +890,7 @@ wxa_status wxa_partition_particles(const wxa_particle_view* src, const wxa_parti
     const PV s = make_pv(*src), d = make_pv(*dst);
     const double* pos = dim == 0 ? s.x : (dim == 1 ? s.y : s.z);
     hipLaunchKernelGGL(partition_flag_kernel, dim3(blocks_for(s.np)), dim3(256), 0, st, pos, s.np, lo, hi, stay, ctr);
-    size_t tmp_bytes = 0;
-    WXA_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, stay, scan, (int)s.np, st));
-    if ((rc = ws->scan_tmp.reserve(tmp_bytes)) != WXA_OK) return rc;
-    WXA_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(ws->scan_tmp.p, tmp_bytes, stay, scan, (int)s.np, st));
+    if ((rc = exclusive_scan(stay, scan, (int)s.np, ws, st)) != WXA_OK) return rc;
     unsigned long long h[3] = {0, 0, 0};
     WXA_HIP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, st));
     WXA_HIP_CHECK(hipStreamSynchronize(st));
@@ -938,8 +926,8 @@ static wxa_status wrap_and_classify_impl(const wxa_particle_view* p, int64_t fir
     }
     hipStream_t st = (hipStream_t)stream;
     wxa_status rc;
-    if ((rc = ws->counters.reserve(512)) != WXA_OK) return rc;
-    unsigned* dcount = (unsigned*)ws->counters.p + (DEST ? 64 : 32);   // words: 0 deposit, 16 gather, 32 classify, 48 walls, 56 injection, 64..90 destinations
+    if ((rc = ws->counters.reserve(COUNTER_BYTES)) != WXA_OK) return rc;
+    unsigned* dcount = (unsigned*)ws->counters.p + (DEST ? CW_DEST : CW_CLASSIFY);
     WXA_HIP_CHECK(hipMemsetAsync(dcount, 0, NL * sizeof(unsigned), st));
     hipLaunchKernelGGL(wrap_classify_kernel<DEST>, dim3(blocks_for(count)), dim3(256), 0, st, p->x, p->y, p->z, p->idcpu,
                        (long)first, (long)count, cg, lists, (long)capacity, dcount);
@@ -1020,8 +1008,8 @@ wxa_status wxa_add_plasma(const wxa_particle_view* dst, const wxa_plasma_injecto
     }
     hipStream_t st = (hipStream_t)stream;
     wxa_status rc;
-    if ((rc = ws->counters.reserve(512)) != WXA_OK) return rc;
-    unsigned long long* dcount = (unsigned long long*)((unsigned*)ws->counters.p + 56);   // 0: deposit, 16: gather, 32: classify, 48: walls
+    if ((rc = ws->counters.reserve(COUNTER_BYTES)) != WXA_OK) return rc;
+    unsigned long long* dcount = (unsigned long long*)((unsigned*)ws->counters.p + CW_INJECT);
     WXA_HIP_CHECK(hipMemsetAsync(dcount, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(add_plasma_kernel, dim3((unsigned)((npoints + 255) / 256)), dim3(256), 0, st, make_pv(*dst), ig, npoints,
                        dcount);
@@ -1082,8 +1070,8 @@ wxa_status wxa_apply_particle_boundaries(const wxa_particle_view* p, const doubl
     WXA_REQUIRE(p->idcpu, "idcpu is needed to retire absorbed particles");
     hipStream_t st = (hipStream_t)stream;
     wxa_status rc;
-    if ((rc = ws->counters.reserve(512)) != WXA_OK) return rc;
-    unsigned* dcount = (unsigned*)ws->counters.p + 48;
+    if ((rc = ws->counters.reserve(COUNTER_BYTES)) != WXA_OK) return rc;
+    unsigned* dcount = (unsigned*)ws->counters.p + CW_WALLS;
     WXA_HIP_CHECK(hipMemsetAsync(dcount, 0, sizeof(unsigned), st));
     hipLaunchKernelGGL(particle_walls_kernel, dim3(blocks_for(p->np)), dim3(256), 0, st, make_pv(*p), wg, dcount);
     WXA_LAUNCH_CHECK();
@@ -1107,39 +1095,46 @@ wxa_status wxa_push_sort_begin(wxa_workspace* ws, int32_t mode, const wxa_partic
     WXA_REQUIRE(s.armed == 0, "wxa_push_sort_begin without the wxa_push_sort_end of the previous one");
     WXA_REQUIRE(p->np < (1L << 31) - 2, "sizes exceed 32-bit sort keys");
     hipStream_t st = (hipStream_t)stream;
-    wxa_status rc;
-    if (mode & WXA_PUSH_SORT_SCATTER) {
-        WXA_REQUIRE(s.pending && s.pending_x == p->x && s.pending_np <= p->np,
-                    "no record of a COUNT on these particle arrays (or they shrank since)");
+    const bool count = mode & WXA_PUSH_SORT_COUNT, scatter = mode & WXA_PUSH_SORT_SCATTER;
+    // Everything that can fail comes first and what arms the pushes last: a begin that is refused leaves the workspace as
+    // it found it.  One thing cannot wait: a lone COUNT writes into the buffers of the record nobody used, so that record
+    // is dropped before they are touched, and stays dropped when an allocation or a memset then fails.
+    if (scatter) {
+        WXA_REQUIRE(s.pending.covers(p), "no record of a COUNT on these particle arrays (or they shrank since)");
         WXA_REQUIRE(pv_ok(dst) && dst->np >= p->np && (p->np == 0 || dst->x != p->x), "the destination tile: out of place, at least as long");
         WXA_REQUIRE((p->idcpu == nullptr) == (dst->idcpu == nullptr), "both tiles with ids or both without");
-        s.dst = *dst;
-        s.appended = p->np - s.pending_np;
     }
-    if (mode & WXA_PUSH_SORT_COUNT) {
+    SortRecord armed;   // the tile being pushed and, for a COUNT, the cell box
+    armed.x = p->x; armed.np = p->np;
+    const int out = scatter ? 1 - s.in : s.in;   // a record nobody used is overwritten
+    if (count) {
         WXA_REQUIRE(plo && dinv && cell_lo && ncell && wrap, "null argument");
         WXA_REQUIRE(ncell[0] > 0 && ncell[1] > 0 && ncell[2] > 0, "empty cell box");
-        const long ncells = (long)((ncell[0] + WXA_TILE - 1) / WXA_TILE) * ((ncell[1] + WXA_TILE - 1) / WXA_TILE) *
-                            ((ncell[2] + WXA_TILE - 1) / WXA_TILE) * (WXA_TILE * WXA_TILE * WXA_TILE);
+        armed = SortRecord::of(p->x, p->np, plo, dinv, cell_lo, ncell);
+        const long ncells = armed.bins;
         WXA_REQUIRE(ncells > 0 && ncells < (1L << 31) - 2, "sizes exceed 32-bit sort keys");
-        s.out = (mode & WXA_PUSH_SORT_SCATTER) ? 1 - s.in : s.in;   // a record nobody used is overwritten
-        if (!(mode & WXA_PUSH_SORT_SCATTER)) s.pending = false;
-        if ((rc = s.kr[s.out].reserve(sizeof(unsigned long long) * (size_t)(p->np + 1))) != WXA_OK) return rc;
+        if (!scatter) s.pending.valid = false;
+        wxa_status rc;
+        if ((rc = s.kr[out].reserve(sizeof(unsigned long long) * (size_t)(p->np + 1))) != WXA_OK) return rc;
         // the histogram and, behind it, the foreign counters; the own counts per cell
         if ((rc = s.hist.reserve(sizeof(int) * 2 * (ncells + 2))) != WXA_OK) return rc;
-        if ((rc = s.offs[s.out].reserve(sizeof(int) * (ncells + 2))) != WXA_OK) return rc;
-        if ((rc = s.own[s.out].reserve(sizeof(int) * (ncells + 2))) != WXA_OK) return rc;
+        if ((rc = s.offs[out].reserve(sizeof(int) * (ncells + 2))) != WXA_OK) return rc;
+        if ((rc = s.own[out].reserve(sizeof(int) * (ncells + 2))) != WXA_OK) return rc;
         WXA_HIP_CHECK(hipMemsetAsync(s.hist.p, 0, sizeof(int) * 2 * (ncells + 2), st));
-        WXA_HIP_CHECK(hipMemsetAsync(s.own[s.out].p, 0, sizeof(int) * (ncells + 2), st));
+        WXA_HIP_CHECK(hipMemsetAsync(s.own[out].p, 0, sizeof(int) * (ncells + 2), st));
+    }
+    // nothing below fails
+    if (count) {
+        s.out = out;
         s.check_retired = check_retired && p->idcpu ? 1 : 0;
         s.predict_dt = predict_dt;
-        for (int d = 0; d < 3; ++d) {
-            s.plo[d] = plo[d]; s.dinv[d] = dinv[d]; s.nc[d] = ncell[d]; s.cell_lo[d] = cell_lo[d]; s.wrap[d] = wrap[d] ? 1 : 0;
-        }
-        s.bins = ncells;
+        for (int d = 0; d < 3; ++d) s.wrap[d] = wrap[d] ? 1 : 0;
     }
-    s.np_armed = p->np;
-    s.count_x = p->x;
+    if (scatter) {
+        s.dst = *dst;
+        s.appended = p->np - s.pending.np;
+    }
+    s.count = armed;
     s.armed = mode;
     return WXA_OK;
 }
@@ -1151,69 +1146,48 @@ wxa_status wxa_push_sort_end(wxa_workspace* ws, int32_t read_live, int64_t* live
     hipStream_t st = (hipStream_t)stream;
     const int32_t mode = s.armed;
     s.armed = 0;
-    *live = s.np_armed;
+    *live = s.count.np;
     *appended = 0;
-    const double* tile_x = nullptr;   // identity of the tile a new record indexes
-    int64_t tile_np = s.np_armed;
+    SortRecord next = s.count;   // what a COUNT leaves: its cell box, on the tile the pushes worked on ...
     if (mode & WXA_PUSH_SORT_SCATTER) {
         // the record's scan becomes the tile offsets of the LDS-tile kernels; the workspace now describes the destination tile
-        std::swap(ws->offsets.p, s.offs[s.in].p);
-        std::swap(ws->offsets.cap, s.offs[s.in].cap);
-        int64_t n_live = s.pending_np;
+        ws->offsets.swap(s.offs[s.in]);
+        int64_t n_live = s.pending.np;
         if (read_live) {   // retired particles were counted: the cell-sorted part ends where their bin starts
             int v = 0;
-            WXA_HIP_CHECK(hipMemcpyAsync(&v, (const int*)ws->offsets.p + s.pending_bins, sizeof(int), hipMemcpyDeviceToHost, st));
+            WXA_HIP_CHECK(hipMemcpyAsync(&v, (const int*)ws->offsets.p + s.pending.bins, sizeof(int), hipMemcpyDeviceToHost, st));
             WXA_HIP_CHECK(hipStreamSynchronize(st));
             n_live = v;
         }
-        ws->sorted_valid = true;
-        ws->sorted_np = n_live;
-        ws->sorted_bins = s.pending_bins;
-        ws->sorted_x = s.dst.x;
-        for (int d = 0; d < 3; ++d) {
-            ws->sort_nc[d] = s.p_nc[d]; ws->sort_cell_lo[d] = s.p_cell_lo[d];
-            ws->sort_plo[d] = s.p_plo[d]; ws->sort_dinv[d] = s.p_dinv[d];
-        }
-        s.pending = false;
+        ws->sorted = s.pending;
+        ws->sorted.valid = true; ws->sorted.x = s.dst.x; ws->sorted.np = n_live;
+        s.pending.valid = false;
         *live = n_live;
         *appended = s.appended;
-        tile_x = s.dst.x;
-        tile_np = n_live + s.appended;
+        next.x = s.dst.x;   // ... or scattered them to
+        next.np = n_live + s.appended;
     }
     if (mode & WXA_PUSH_SORT_COUNT) {
-        size_t tmp_bytes = 0;
-        int* hist = (int*)s.hist.p;
-        int* offs = (int*)s.offs[s.out].p;
-        WXA_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, hist, offs, (int)(s.bins + 2), st));
-        wxa_status rc;
-        if ((rc = ws->scan_tmp.reserve(tmp_bytes)) != WXA_OK) return rc;
-        WXA_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(ws->scan_tmp.p, tmp_bytes, hist, offs, (int)(s.bins + 2), st));
+        const wxa_status rc = exclusive_scan((int*)s.hist.p, (int*)s.offs[s.out].p, (int)(next.bins + 2), ws, st);
+        if (rc != WXA_OK) return rc;
         s.in = s.out;
-        s.pending = true;
-        s.pending_np = tile_np;
-        s.pending_bins = s.bins;
-        s.pending_x = tile_x ? tile_x : nullptr;   // COUNT alone: set by the caller's view, below
-        for (int d = 0; d < 3; ++d) {
-            s.p_nc[d] = s.nc[d]; s.p_cell_lo[d] = s.cell_lo[d]; s.p_plo[d] = s.plo[d]; s.p_dinv[d] = s.dinv[d];
-        }
-        if (!tile_x) s.pending_x = s.count_x;
+        s.pending = next;
     }
     return WXA_OK;
 }
 
 int32_t wxa_push_sort_pending(const wxa_workspace* ws, const wxa_particle_view* p) {
-    return ws && p && ws->ps.pending && ws->ps.pending_x == p->x && ws->ps.pending_np <= p->np ? 1 : 0;
+    return ws && p && ws->ps.pending.covers(p) ? 1 : 0;
 }
 
 wxa_status wxa_sort_live_count(wxa_workspace* ws, int64_t* n, void* stream) {
     WXA_REQUIRE(ws && n, "null argument");
-    WXA_REQUIRE(ws->sorted_valid, "no sort recorded in this workspace");
+    WXA_REQUIRE(ws->sorted.valid, "no sort recorded in this workspace");
     int live = 0;
     hipStream_t st = (hipStream_t)stream;
-    WXA_HIP_CHECK(hipMemcpyAsync(&live, (const int*)ws->offsets.p + ws->sorted_bins, sizeof(int),
-                                 hipMemcpyDeviceToHost, st));
+    WXA_HIP_CHECK(hipMemcpyAsync(&live, (const int*)ws->offsets.p + ws->sorted.bins, sizeof(int), hipMemcpyDeviceToHost, st));
     WXA_HIP_CHECK(hipStreamSynchronize(st));
-    ws->sorted_np = live;
+    ws->sorted.np = live;
     *n = live;
     return WXA_OK;
 }

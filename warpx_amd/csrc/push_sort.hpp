@@ -181,6 +181,14 @@ __device__ __forceinline__ void push_sort_tile_finish(const H* h, const int* lds
     }
 }
 
+// the key of a record's cell box
+inline SortGeom sort_geom_of(const SortRecord& r, const int32_t* wrap = nullptr) {
+    SortGeom sg;
+    for (int d = 0; d < 3; ++d) { sg.plo[d] = r.plo[d]; sg.dinv[d] = r.dinv[d]; sg.nc[d] = r.nc[d]; sg.wrap[d] = wrap ? wrap[d] : 0; }
+    sg.retired_bin = (int)r.bins;
+    return sg;
+}
+
 // the hook of a push kernel whose particle view starts `first` particles into the tile (nothing armed, no workspace or
 // a push that does not move the particles: an inert hook)
 inline PushSort make_push_sort(const wxa_workspace* ws, const long first, const bool move) {
@@ -190,13 +198,12 @@ inline PushSort make_push_sort(const wxa_workspace* ws, const long first, const 
     h.mode = s.armed;
     h.first = first;
     if (s.armed & PUSH_SORT_COUNT) {
-        for (int d = 0; d < 3; ++d) { h.sg.plo[d] = s.plo[d]; h.sg.dinv[d] = s.dinv[d]; h.sg.nc[d] = s.nc[d]; h.sg.wrap[d] = s.wrap[d]; }
-        h.sg.retired_bin = (int)s.bins;
+        h.sg = sort_geom_of(s.count, s.wrap);
         h.check_retired = s.check_retired;
         h.predict_dt = s.predict_dt;
         h.kr_out = (unsigned long long*)s.kr[s.out].p;
         h.hist = (int*)s.hist.p;
-        h.fcnt = (int*)s.hist.p + (s.bins + 2);
+        h.fcnt = (int*)s.hist.p + (s.count.bins + 2);
         h.own_out = (int*)s.own[s.out].p;
     }
     if (s.armed & PUSH_SORT_SCATTER) {
@@ -206,9 +213,9 @@ inline PushSort make_push_sort(const wxa_workspace* ws, const long first, const 
         h.dx = s.dst.x; h.dy = s.dst.y; h.dz = s.dst.z; h.dw = s.dst.w;
         h.dux = s.dst.ux; h.duy = s.dst.uy; h.duz = s.dst.uz;
         h.did = (unsigned long long*)s.dst.idcpu;
-        h.np_counted = s.pending_np;
+        h.np_counted = s.pending.np;
         h.n_appended = s.appended;
-        h.retired_bin_in = (int)s.pending_bins;
+        h.retired_bin_in = (int)s.pending.bins;
     }
     return h;
 }

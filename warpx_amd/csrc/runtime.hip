@@ -28,14 +28,7 @@ wxa_status wxa_workspace_create(wxa_workspace** ws) {
     return WXA_OK;
 }
 
-void wxa_workspace_destroy(wxa_workspace* ws) {
-    if (!ws) return;
-    ws->cell.release(); ws->rank.release(); ws->hist.release(); ws->offsets.release();
-    ws->scan_tmp.release(); ws->tile_offsets.release(); ws->stragglers.release(); ws->counters.release(); ws->lens_tab.release(); ws->ext_pp.release();
-    for (int b = 0; b < 2; ++b) { ws->ps.kr[b].release(); ws->ps.offs[b].release(); ws->ps.own[b].release(); }
-    ws->ps.hist.release(); ws->heavy.release();
-    delete ws;
-}
+void wxa_workspace_destroy(wxa_workspace* ws) { delete ws; }   // every buffer is a DevBuf: released by its destructor
 
 wxa_status wxa_workspace_set_external_particle_fields(wxa_workspace* ws, const double E[3], const double B[3]) {
     WXA_REQUIRE(ws && E && B, "null argument");

@@ -39,15 +39,15 @@ struct TileLaunch {
     unsigned groups = 0;            // workgroups of the tile kernel: the regular grid and the heavy tiles' extra units
 };
 
-// The launch of a tile kernel over the `np` sorted particles of ws.  The straggler count is the two-slot counter at
+// The launch of a tile kernel over the `np` sorted particles of ws->sorted.  The straggler count is the two-slot counter at
 // words `counter_word`, `counter_word + 1` of ws->counters, flipped `flips` times so far.  Everything that can fail comes
 // first and the flip last: a launch that is not made leaves the counter protocol where it was.  On `st`, in this order:
 // the planning of the heavy tiles (its memset and kernel, if any tile can be heavy), then -- once per workspace -- the
 // memset of the counters; the caller's tile kernel follows.
-inline wxa_status plan_tile_launch(wxa_workspace* ws, long np, int counter_word, unsigned& flips, hipStream_t st, TileLaunch& tl) {
+inline wxa_status plan_tile_launch(wxa_workspace* ws, long np, CounterWord counter_word, unsigned& flips, hipStream_t st, TileLaunch& tl) {
     for (int d = 0; d < 3; ++d) {
-        tl.tg.nt[d] = (ws->sort_nc[d] + WXA_TILE - 1) / WXA_TILE;
-        tl.tg.cell_lo[d] = ws->sort_cell_lo[d];
+        tl.tg.nt[d] = ws->sorted.tiles(d);
+        tl.tg.cell_lo[d] = ws->sorted.cell_lo[d];
     }
     tl.ntiles = (long)tl.tg.nt[0] * tl.tg.nt[1] * tl.tg.nt[2];
     tl.offsets = (const int*)ws->offsets.p;

@@ -9,10 +9,14 @@
 
 namespace wxa {
 
-// grow-only device buffer
+// grow-only device buffer; owns its memory
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
     wxa_status reserve(size_t bytes) {
         if (bytes <= cap) return WXA_OK;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -24,28 +28,58 @@ struct DevBuf {
         cap = want;
         return WXA_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+
+// Which cell sort a set of offsets describes: the particle array, how many of its particles they cover, the cell box.
+// The workspace keeps three: the last sort, the record a COUNT left, and what is armed between begin and end.
+struct SortRecord {
+    bool valid = false;
+    const double* x = nullptr;   // identity of the particle array
+    int64_t np = 0;              // particles covered (of the last sort: the live ones after wxa_sort_live_count)
+    int64_t bins = 0;            // cell bins (the retired bin follows)
+    int32_t nc[3] = {0, 0, 0}, cell_lo[3] = {0, 0, 0};
+    double plo[3] = {0, 0, 0}, dinv[3] = {0, 0, 0};   // physical lower corner of the cell box; cells are numbered from cell_lo
+
+    // the first np particles of view p are the ones this record describes
+    bool covers(const wxa_particle_view* p) const { return valid && x == p->x && np <= p->np; }
+    static int tiles_of(int n) { return (n + WXA_TILE - 1) / WXA_TILE; }
+    int tiles(int d) const { return tiles_of(nc[d]); }   // tiles per direction
+    // cell bins of a box: whole tiles of WXA_TILE^3 cells
+    static long bins_of(const int32_t nc[3]) {
+        return (long)tiles_of(nc[0]) * tiles_of(nc[1]) * tiles_of(nc[2]) * (WXA_TILE * WXA_TILE * WXA_TILE);
+    }
+    static SortRecord of(const double* x, int64_t np, const double plo[3], const double dinv[3], const int32_t cell_lo[3],
+                         const int32_t nc[3]) {
+        SortRecord r;
+        r.valid = true; r.x = x; r.np = np; r.bins = bins_of(nc);
+        for (int d = 0; d < 3; ++d) { r.nc[d] = nc[d]; r.cell_lo[d] = cell_lo[d]; r.plo[d] = plo[d]; r.dinv[d] = dinv[d]; }
+        return r;
+    }
+};
+
+// ws->counters: COUNTER_BYTES of 32-bit words, the first word of each user
+enum CounterWord : int {
+    CW_DEPOSIT = 0,     // 0, 1: stragglers of the LDS-tile deposition, two slots (flip_counter)
+    CW_GATHER = 16,     // 16, 17: stragglers of the LDS-tile gather, two slots
+    CW_CLASSIFY = 32,   // 32 .. 37: the six lists of wxa_wrap_and_classify
+    CW_WALLS = 48,      // particles lost to wxa_apply_particle_boundaries
+    CW_INJECT = 56,     // 56, 57: particles added by wxa_add_plasma (64 bits)
+    CW_DEST = 64,       // 64 .. 90: the 27 lists of wxa_wrap_and_classify_dest
+    COUNTER_BYTES = 512
 };
 
 }  // namespace wxa
 
 struct wxa_workspace {
-    wxa::DevBuf cell, rank, hist, offsets, scan_tmp, tile_offsets, stragglers, counters;
+    wxa::DevBuf cell, rank, hist, offsets, scan_tmp, stragglers, counters;
     wxa::DevBuf heavy;   // units per tile and the extra workgroups of the tiles that are split (heavy_tiles.hpp)
     // The straggler counts of the two LDS-tile kernels live in two slots each: launch n counts in slot n & 1, which launch
     // n - 1's tile kernel left at zero, and zeroes the other one for launch n + 1 -- no fill dispatch in front of the kernel
     // (round 6: a 4-byte hipMemsetAsync is a dispatch of 5 us; wxa::flip_counter below)
     bool flip_ready = false;
     unsigned gather_flips = 0, deposit_flips = 0;
-    // description of the last cell sort (consumed by the tile-based deposition)
-    bool sorted_valid = false;
-    int64_t sorted_np = 0;              // particles covered by the tile offsets (live ones after wxa_sort_live_count)
-    int64_t sorted_bins = 0;            // number of cell bins of that sort (the retired bin follows)
-    const double* sorted_x = nullptr;   // identity of the sorted particle array
-    int32_t sort_nc[3] = {0, 0, 0};
-    int32_t sort_cell_lo[3] = {0, 0, 0};
-    double sort_plo[3] = {0, 0, 0};
-    double sort_dinv[3] = {0, 0, 0};
+    // the last cell sort: ws->offsets are its tile offsets (consumed by the LDS-tile kernels and the wrap through the sort)
+    wxa::SortRecord sorted;
     // particles.E_external_particle / B_external_particle of the container that owns this workspace
     // (wxa_workspace_set_external_particle_fields); added to the gathered fields in PushPX / PushP
     double ext_eb[6] = {0, 0, 0, 0, 0, 0};
@@ -69,28 +103,21 @@ struct wxa_workspace {
         int32_t check_retired = 0;           // armed COUNT: the caller's tile may hold retired particles
         double predict_dt = 0.0;             // armed COUNT: keys of the positions this much free flight ahead
         int32_t in = 0, out = 0;             // kr[in], offs[in]: the pending record; [out]: what the armed COUNT writes
-        bool pending = false;
-        int64_t pending_np = 0, pending_bins = 0;
-        const double* pending_x = nullptr;   // identity of the tile the record indexes
-        int32_t p_nc[3] = {0, 0, 0}, p_cell_lo[3] = {0, 0, 0};   // geometry of the pending record
-        double p_plo[3] = {0, 0, 0}, p_dinv[3] = {0, 0, 0};
-        int32_t nc[3] = {0, 0, 0}, cell_lo[3] = {0, 0, 0}, wrap[3] = {0, 0, 0};   // geometry of the armed COUNT
-        double plo[3] = {0, 0, 0}, dinv[3] = {0, 0, 0};
-        int64_t bins = 0;
+        wxa::SortRecord pending;             // the record kr[in], offs[in], own[in] hold, on the tile it indexes
+        wxa::SortRecord count;               // armed: the tile being pushed (x, np) and, for a COUNT, the cell box it keys
+        int32_t wrap[3] = {0, 0, 0};         // armed COUNT: the periodic directions
         wxa_particle_view dst{};             // armed SCATTER: the destination tile
-        int64_t np_armed = 0;                // particles of the tile being pushed
-        const double* count_x = nullptr;     // ... and its identity
         int64_t appended = 0;                // armed SCATTER: particles appended since the record was taken
     } ps;
 };
 
 namespace wxa {
 // words `word`, `word + 1` of ws->counters as a two-slot counter (see wxa_workspace::flip_ready)
-inline wxa_status flip_counter(wxa_workspace* ws, int word, unsigned& flips, hipStream_t st, unsigned*& cur, unsigned*& next) {
+inline wxa_status flip_counter(wxa_workspace* ws, CounterWord word, unsigned& flips, hipStream_t st, unsigned*& cur, unsigned*& next) {
     wxa_status rc;
-    if ((rc = ws->counters.reserve(512)) != WXA_OK) return rc;
+    if ((rc = ws->counters.reserve(COUNTER_BYTES)) != WXA_OK) return rc;
     if (!ws->flip_ready) {   // once per workspace
-        WXA_HIP_CHECK(hipMemsetAsync(ws->counters.p, 0, 512, st));
+        WXA_HIP_CHECK(hipMemsetAsync(ws->counters.p, 0, COUNTER_BYTES, st));
         ws->flip_ready = true;
     }
     unsigned* base = (unsigned*)ws->counters.p + word;
@@ -126,10 +153,8 @@ inline ExtLens lens_of(const wxa_workspace* ws) {
     L.tab = (const double*)ws->lens_tab.p;
     return L;
 }
-// the LDS-tile kernels can take p: its first ws->sorted_np particles are those of the last cell sort
-inline bool sorted_tiles_available(const wxa_workspace* ws, const wxa_particle_view* p) {
-    return ws && ws->sorted_valid && ws->sorted_x == p->x && ws->sorted_np <= p->np;
-}
+// the LDS-tile kernels can take p: its first ws->sorted.np particles are those of the last cell sort
+inline bool sorted_tiles_available(const wxa_workspace* ws, const wxa_particle_view* p) { return ws && ws->sorted.covers(p); }
 // LDS-tile deposition (deposit_tile.hip)
 wxa_status deposit_current_tiled(const wxa_particle_view* p, const wxa_field_view J[3],
                                  const wxa_grid_geom* geom, double q, double dt, double relative_time,
