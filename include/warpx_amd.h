@@ -401,7 +401,26 @@ wxa_status wxa_apply_pec_b(const wxa_field_view B[3], const int32_t dom_lo[3],
                            const int32_t dom_hi[3], const int32_t pec_lo[3],
                            const int32_t pec_hi[3], const int32_t ng[3], void* stream);
 
-#define WXA_PBOUNDARY_DEFAULT    0   /* periodic where the field boundary is periodic, absorbing where it is PEC */
+#define WXA_BOUNDARY_SILVER_MUELLER 2   /* boundary.field_lo/hi = absorbing_silver_mueller */
+
+/* Replaces FiniteDifferenceSolver::ApplySilverMuellerBoundary, 3-D Cartesian branch
+ * (Source/FieldSolver/FiniteDifferenceSolver/ApplySilverMuellerBoundary.cpp:173-350), which
+ * WarpX::ApplyBfieldBoundary calls after the first half update of B only
+ * (Source/BoundaryConditions/WarpXFieldBoundaries.cpp:132-146) with the full time step dt.
+ * With r = c dt dinv[d], coef1 = (1 - r)/(1 + r), coef2 = 2 r/(1 + r)/c (:177-188), the tangential
+ * components of B in the first guard plane behind a flagged face, index dom_hi[d] + 1 or dom_lo[d] - 1
+ * along d, become coef1 B -+ coef2 E (point rules :238-346) over the valid box of the component grown
+ * by one point (:230-232); a point on two such planes takes both updates in the reference's order.
+ * Every other point of B, and all of E, is left as it is; a brick that holds none of those planes
+ * launches nothing.  dom_lo/dom_hi as for wxa_apply_pec_e; sm_lo[d] / sm_hi[d] != 0 marks the faces.
+ * One launch for all faces and components.  Yee staggering only (WXA_ERR_UNSUPPORTED otherwise,
+ * Source/WarpX.cpp:829-832); needs 1 guard point on E and B. */
+wxa_status wxa_apply_silver_mueller(const wxa_field_view E[3], const wxa_field_view B[3], double dt,
+                                    const double dinv[3], const int32_t dom_lo[3], const int32_t dom_hi[3],
+                                    const int32_t sm_lo[3], const int32_t sm_hi[3], void* stream);
+
+#define WXA_PBOUNDARY_DEFAULT    0   /* periodic where the field boundary is periodic, absorbing where it is PEC or
+                                        Silver-Mueller */
 #define WXA_PBOUNDARY_ABSORBING  1   /* boundary.particle_lo/hi = absorbing  */
 #define WXA_PBOUNDARY_REFLECTING 2   /* boundary.particle_lo/hi = reflecting */
 #define WXA_PBOUNDARY_PERIODIC   3   /* boundary.particle_lo/hi = periodic   */
@@ -549,7 +568,8 @@ typedef struct wxa_sim_config {
     int32_t coord[3];            /* this brick's coordinates                    */
     int32_t field_boundary_lo[3];/* boundary.field_lo: WXA_BOUNDARY_* (0 = periodic, the default) */
     int32_t field_boundary_hi[3];/* boundary.field_hi; PEC only along unsplit directions (J next to a wall
-                                    is folded back with the image-charge sign of an absorbing wall) */
+                                    is folded back with the image-charge sign of an absorbing wall);
+                                    WXA_BOUNDARY_SILVER_MUELLER along any direction, Yee solver only */
     int32_t particle_boundary_lo[3]; /* boundary.particle_lo: WXA_PBOUNDARY_* (0 = default)              */
     int32_t particle_boundary_hi[3]; /* boundary.particle_hi                                             */
     int32_t overlap_halo;        /* 1 (bricks, all-periodic runs): the guard exchanges travel on a second stream --

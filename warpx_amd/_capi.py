@@ -143,7 +143,7 @@ class RcclStats(C.Structure):
 RCCL_LOOPBACK, RCCL_TIMING = 1, 2
 PUSHER_BORIS, PUSHER_VAY, PUSHER_HC, PUSHER_BORIS_RR = 0, 1, 2, 3
 DEPOSIT_ESIRKEPOV, DEPOSIT_DIRECT = 0, 1
-BOUNDARY_PERIODIC, BOUNDARY_PEC = 0, 1
+BOUNDARY_PERIODIC, BOUNDARY_PEC, BOUNDARY_SILVER_MUELLER = 0, 1, 2
 PBOUNDARY_DEFAULT, PBOUNDARY_ABSORBING, PBOUNDARY_REFLECTING, PBOUNDARY_PERIODIC = 0, 1, 2, 3
 
 _FV3 = FieldView * 3
@@ -284,6 +284,8 @@ _PRODUCT_SIGS = {
     "pack_box_f32": (C.c_int, [_PFV, _I32_3, _I32_3, C.c_void_p, C.c_void_p]),
     "unpack_box_f32": (C.c_int, [_PFV, _I32_3, _I32_3, C.c_void_p, C.c_int, C.c_void_p]),
     "field_set_zero_multi": (C.c_int, [_PFV, C.c_int32, C.c_void_p]),
+    # E, B, dt, dinv, dom_lo, dom_hi, sm_lo, sm_hi, stream (the oracle has no Silver-Mueller boundary)
+    "apply_silver_mueller": (C.c_int, [_FV3, _FV3, C.c_double, _D3, _I32_3, _I32_3, _I32_3, _I32_3, C.c_void_p]),
     "copy_to_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "copy_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "device_synchronize": (C.c_int, []),

@@ -283,6 +283,56 @@ evolve_b_faces_kernel(DevF Ex, DevF Ey, DevF Ez, DevF Bx, DevF By, DevF Bz, Face
     }
 }
 
+// ---- Silver-Mueller absorbing boundary (ApplySilverMuellerBoundary.cpp:173-350, 3-D branch) --------------
+// The guard planes of B right behind the flagged faces, all faces and all three components in one launch, one lane per
+// point (E is only read).  A component lives on the planes of the two directions it is cell-centred along; a point on
+// two planes (an edge of the box) belongs to the box of the first direction and takes both updates there, in the
+// reference's order (the lower direction first, its hi face before its lo face).  A box is one point thick along its
+// face's direction: lanes run along i on the y and z planes and, the x planes being one point per row, along j there.
+struct SmFaces {
+    int n;
+    Box3 b[12];                  // (plane, component) boxes
+    int comp[12];
+    int second[12];              // the plane of the component's second direction: edge points are left to the first
+    long first[13];              // running point counts
+    int plane_lo[3], plane_hi[3];   // dom_lo - 1 / dom_hi + 1 where this brick applies the condition, else INT_MIN
+    double coef1[3], coef2[3];
+};
+// B_C on the planes of its directions D1 < D2; Ea / Eb: the components of E the two rules read (the third axis each).
+// The sign of the hi-face rule is that of the permutation (C, D, third axis); the lo face has the other sign and
+// reads E one point further in.
+template <int C>
+__device__ inline void silver_mueller_point(const DevF& B, const DevF& Ea, const DevF& Eb, const SmFaces& sf, int second,
+                                            int i, int j, int k) {
+    constexpr int D1 = C == 0 ? 1 : 0, D2 = C == 2 ? 1 : 2;
+    constexpr double S1 = (D1 - C + 3) % 3 == 1 ? 1.0 : -1.0, S2 = (D2 - C + 3) % 3 == 1 ? 1.0 : -1.0;
+    const int ijk[3] = {i, j, k};
+    const bool hi1 = ijk[D1] == sf.plane_hi[D1], lo1 = ijk[D1] == sf.plane_lo[D1];
+    if (second && (hi1 || lo1)) return;
+    double* b = B.p + B.off(i, j, k);
+    double v = *b;
+    if (hi1) v = sf.coef1[D1] * v + (S1 * sf.coef2[D1]) * Ea(i, j, k);
+    if (lo1) v = sf.coef1[D1] * v + (-S1 * sf.coef2[D1]) * Ea(i + (D1 == 0), j + (D1 == 1), k);
+    if (ijk[D2] == sf.plane_hi[D2]) v = sf.coef1[D2] * v + (S2 * sf.coef2[D2]) * Eb(i, j, k);
+    if (ijk[D2] == sf.plane_lo[D2]) v = sf.coef1[D2] * v + (-S2 * sf.coef2[D2]) * Eb(i, j + (D2 == 1), k + (D2 == 2));
+    *b = v;
+}
+__global__ void __launch_bounds__(256)
+apply_silver_mueller_kernel(DevF Ex, DevF Ey, DevF Ez, DevF Bx, DevF By, DevF Bz, SmFaces sf) {
+    long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= sf.first[sf.n]) return;
+    int f = 0;
+    while (t >= sf.first[f + 1]) ++f;
+    t -= sf.first[f];
+    const Box3 b = sf.b[f];
+    const int n0 = b.hi[0] - b.lo[0], n1 = b.hi[1] - b.lo[1];
+    const int i = b.lo[0] + (int)(t % n0), j = b.lo[1] + (int)((t / n0) % n1), k = b.lo[2] + (int)(t / ((long)n0 * n1));
+    const int c = sf.comp[f];
+    if (c == 0) silver_mueller_point<0>(Bx, Ez, Ey, sf, sf.second[f], i, j, k);        // :238-256
+    else if (c == 1) silver_mueller_point<1>(By, Ez, Ex, sf, sf.second[f], i, j, k);   // :279-299
+    else silver_mueller_point<2>(Bz, Ey, Ex, sf, sf.second[f], i, j, k);               // :322-342
+}
+
 // generic box copy kernels -----------------------------------------------------
 struct BoxN {
     int lo[3];
@@ -976,6 +1026,67 @@ wxa_status wxa_evolve_b_guard_layer(const wxa_field_view E[3], const wxa_field_v
         hipLaunchKernelGGL(evolve_b_faces_kernel, dim3((unsigned)((fb.first[fb.n] + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            make_devf(E[0]), make_devf(E[1]), make_devf(E[2]), make_devf(B[0]), make_devf(B[1]), make_devf(B[2]),
                            fb, dt, dinv[0], dinv[1], dinv[2]);
+    WXA_LAUNCH_CHECK();
+    return WXA_OK;
+}
+
+// FiniteDifferenceSolver::ApplySilverMuellerBoundary, 3-D branch (ApplySilverMuellerBoundary.cpp:173-350): on the
+// valid box of each component of B grown by one point (:230-232), the points of the planes dom_hi[d] + 1 / dom_lo[d] - 1
+// of the flagged faces.  A brick none of those planes passes through launches nothing.
+wxa_status wxa_apply_silver_mueller(const wxa_field_view E[3], const wxa_field_view B[3], double dt, const double dinv[3],
+                                    const int32_t dom_lo[3], const int32_t dom_hi[3], const int32_t sm_lo[3],
+                                    const int32_t sm_hi[3], void* stream) {
+    WXA_REQUIRE(E && B && dinv && dom_lo && dom_hi && sm_lo && sm_hi, "null argument");
+    for (int c = 0; c < 3; ++c) WXA_REQUIRE(view_ok(E[c]) && view_ok(B[c]), "bad field view");
+    if (!yee_E(E) || !yee_B(B)) {
+        set_last_error("wxa_apply_silver_mueller: only the Yee staggering is supported");
+        return WXA_ERR_UNSUPPORTED;
+    }
+    for (int c = 1; c < 3; ++c)   // one brick: the planes found for one component are those of the others
+        for (int d = 0; d < 3; ++d)
+            WXA_REQUIRE(valid_box(B[c]).lo[d] == valid_box(B[0]).lo[d] &&
+                        valid_box(B[c]).hi[d] - B[c].stag[d] == valid_box(B[0]).hi[d] - B[0].stag[d],
+                        "the components of B cover different cells");
+    SmFaces sf;
+    sf.n = 0;
+    sf.first[0] = 0;
+    for (int d = 0; d < 3; ++d) {
+        const double r = PhysConst::c * dt * dinv[d];                 // :177-188
+        sf.coef1[d] = (1. - r) / (1. + r);
+        sf.coef2[d] = 2. * r / (1. + r) / PhysConst::c;
+        sf.plane_lo[d] = sf.plane_hi[d] = INT_MIN;
+    }
+    for (int c = 0; c < 3; ++c) {
+        Box3 g = valid_box(B[c]);
+        for (int d = 0; d < 3; ++d) { g.lo[d] -= 1; g.hi[d] += 1; }
+        bool first_dir = true;
+        for (int d = 0; d < 3; ++d) {
+            if (d == c) continue;   // nodal along its own direction: no rule there
+            for (int side = 1; side >= 0; --side) {
+                if (!(side == 0 ? sm_lo[d] : sm_hi[d])) continue;
+                const int plane = side == 0 ? dom_lo[d] - 1 : dom_hi[d] + 1;
+                if (plane < g.lo[d] || plane >= g.hi[d]) continue;   // not this brick's face
+                (side == 0 ? sf.plane_lo[d] : sf.plane_hi[d]) = plane;
+                Box3 b = g;
+                b.lo[d] = plane; b.hi[d] = plane + 1;
+                // every point the rule touches lies inside the arrays: B itself, and the third component of E at the
+                // same indices (hi face) or one point further in along d (lo face)
+                const wxa_field_view& Ee = E[3 - c - d];
+                int32_t elo[3] = {b.lo[0], b.lo[1], b.lo[2]}, ehi[3] = {b.hi[0], b.hi[1], b.hi[2]};
+                WXA_REQUIRE(box_inside(B[c], elo, ehi), "Silver-Mueller needs 1 guard point on B");
+                if (side == 0) { elo[d] += 1; ehi[d] += 1; }
+                WXA_REQUIRE(box_inside(Ee, elo, ehi), "Silver-Mueller needs 1 guard point on E");
+                sf.b[sf.n] = b; sf.comp[sf.n] = c; sf.second[sf.n] = first_dir ? 0 : 1;
+                sf.first[sf.n + 1] = sf.first[sf.n] + (long)(b.hi[0] - b.lo[0]) * (b.hi[1] - b.lo[1]) * (b.hi[2] - b.lo[2]);
+                ++sf.n;
+            }
+            first_dir = false;
+        }
+    }
+    if (sf.n > 0 && sf.first[sf.n] > 0)
+        hipLaunchKernelGGL(apply_silver_mueller_kernel, dim3((unsigned)((sf.first[sf.n] + 255) / 256)), dim3(256), 0,
+                           (hipStream_t)stream, make_devf(E[0]), make_devf(E[1]), make_devf(E[2]), make_devf(B[0]),
+                           make_devf(B[1]), make_devf(B[2]), sf);
     WXA_LAUNCH_CHECK();
     return WXA_OK;
 }

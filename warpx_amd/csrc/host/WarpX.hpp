@@ -168,21 +168,33 @@ public:
             if (m_ctx.brick_box.length(d) < guard_cells.ng_alloc_J[d] + 1)
                 throw std::runtime_error("brick thinner than the guard depth");
         m_comm = std::make_unique<BrickComm>(be, comm, cfg.nbricks, cfg.coord);
-        // boundary.field_lo / field_hi (Source/WarpX.cpp, ReadBoundaryConditions): periodic or PEC
+        // boundary.field_lo / field_hi (Source/WarpX.cpp, ReadBoundaryConditions): periodic, PEC or Silver-Mueller;
+        // the two faces of a non-periodic direction may differ
         int periodic[3];
         for (int d = 0; d < 3; ++d) {
             const int lo = cfg.field_boundary_lo[d], hi = cfg.field_boundary_hi[d];
-            const bool ok = (lo == WXA_BOUNDARY_PERIODIC || lo == WXA_BOUNDARY_PEC) &&
-                            (hi == WXA_BOUNDARY_PERIODIC || hi == WXA_BOUNDARY_PEC) &&
-                            ((lo == WXA_BOUNDARY_PERIODIC) == (hi == WXA_BOUNDARY_PERIODIC));
+            auto known = [](int b) {
+                return b == WXA_BOUNDARY_PERIODIC || b == WXA_BOUNDARY_PEC || b == WXA_BOUNDARY_SILVER_MUELLER;
+            };
+            const bool ok = known(lo) && known(hi) && ((lo == WXA_BOUNDARY_PERIODIC) == (hi == WXA_BOUNDARY_PERIODIC));
             if (!ok) throw std::runtime_error("field boundary: a direction is periodic on both sides or on neither");
             periodic[d] = lo == WXA_BOUNDARY_PERIODIC;
             // a wall belongs to the bricks that touch it; the schedule (which exchanges are issued) follows the
             // domain's walls, the same on every brick
             m_pec_lo[d] = lo == WXA_BOUNDARY_PEC && cfg.coord[d] == 0;
             m_pec_hi[d] = hi == WXA_BOUNDARY_PEC && cfg.coord[d] == cfg.nbricks[d] - 1;
-            m_any_pec = m_any_pec || lo == WXA_BOUNDARY_PEC || hi == WXA_BOUNDARY_PEC;
+            m_sm_lo[d] = lo == WXA_BOUNDARY_SILVER_MUELLER && cfg.coord[d] == 0;
+            m_sm_hi[d] = hi == WXA_BOUNDARY_SILVER_MUELLER && cfg.coord[d] == cfg.nbricks[d] - 1;
+            m_any_wall = m_any_wall || !periodic[d];
             m_pec_here = m_pec_here || m_pec_lo[d] || m_pec_hi[d];
+            m_sm_here = m_sm_here || m_sm_lo[d] || m_sm_hi[d];
+            if (lo == WXA_BOUNDARY_SILVER_MUELLER || hi == WXA_BOUNDARY_SILVER_MUELLER) {
+                if (!be->apply_silver_mueller)
+                    throw std::runtime_error("field boundary absorbing_silver_mueller: this backend has no Silver-Mueller kernel");
+                if (cfg.maxwell_solver != WXA_SOLVER_YEE)   // Source/WarpX.cpp:829-832
+                    throw std::runtime_error("field boundary absorbing_silver_mueller can only be used with the Yee solver "
+                                             "(algo.maxwell_solver = yee)");
+            }
             m_dom_lo[d] = 0;
             m_dom_hi[d] = cfg.n_cell[d] - 1;
         }
@@ -541,7 +553,7 @@ public:
     void SetUpHaloOverlap(bool want) {
         // a wall's boundary kernel owns the guards behind it; WXA_NO_GUARD_LAYER=1 brings the exchange back (debugging)
         // (the guard-layer kernel is the Yee update: with CKC the reference's exchange stays)
-        m_grown_b = !m_any_pec && m_be->evolve_b_guard_layer != nullptr && m_cfg.maxwell_solver == WXA_SOLVER_YEE &&
+        m_grown_b = !m_any_wall && m_be->evolve_b_guard_layer != nullptr && m_cfg.maxwell_solver == WXA_SOLVER_YEE &&
                     !m_env_no_guard_layer;
         m_overlap = false;
         bool any_split = false;
@@ -752,7 +764,7 @@ public:
             const int32_t grow[3] = {1, 1, 1};
             m_fdtd_solver_fp->EvolveBGuardLayer(m_fields, 0, a_dt, grow);
         }
-        ApplyBfieldBoundary(0, PatchType::fine);                        // :926
+        ApplyBfieldBoundary(0, PatchType::fine, a_dt_type);             // :926
     }
     // :930-1011
     void EvolveE(amrex::Real a_dt) {
@@ -772,14 +784,23 @@ public:
         if (m_be->apply_pec_e(Ev, m_dom_lo, m_dom_hi, m_pec_lo, m_pec_hi, ng, m_ctx.stream) != 0)
             throw std::runtime_error("apply_pec_e failed");
     }
-    // :108-135 -> PEC::ApplyPECtoBfield (WarpX_PEC.cpp:540-626)
-    void ApplyBfieldBoundary(int /*lev*/, PatchType /*patch_type*/) {
-        if (!m_pec_here) return;
+    // :108-135 -> PEC::ApplyPECtoBfield (WarpX_PEC.cpp:540-626); :132-146 -> ApplySilverMuellerBoundary
+    // (ApplySilverMuellerBoundary.cpp:173-350) after the first half update only, with the full time step
+    void ApplyBfieldBoundary(int /*lev*/, PatchType /*patch_type*/, DtType a_dt_type) {
+        if (!m_pec_here && !(m_sm_here && a_dt_type == DtType::FirstHalf)) return;
         auto B = m_fields.get_alldirs(warpx::fields::FieldType::Bfield_fp, 0);
         const wxa_field_view Bv[3] = {B[0]->view(), B[1]->view(), B[2]->view()};
-        const int32_t ng[3] = {guard_cells.ng_FieldGather[0], guard_cells.ng_FieldGather[1], guard_cells.ng_FieldGather[2]};
-        if (m_be->apply_pec_b(Bv, m_dom_lo, m_dom_hi, m_pec_lo, m_pec_hi, ng, m_ctx.stream) != 0)
-            throw std::runtime_error("apply_pec_b failed");
+        if (m_pec_here) {
+            const int32_t ng[3] = {guard_cells.ng_FieldGather[0], guard_cells.ng_FieldGather[1], guard_cells.ng_FieldGather[2]};
+            if (m_be->apply_pec_b(Bv, m_dom_lo, m_dom_hi, m_pec_lo, m_pec_hi, ng, m_ctx.stream) != 0)
+                throw std::runtime_error("apply_pec_b failed");
+        }
+        if (m_sm_here && a_dt_type == DtType::FirstHalf) {
+            auto E = m_fields.get_alldirs(warpx::fields::FieldType::Efield_fp, 0);
+            const wxa_field_view Ev[3] = {E[0]->view(), E[1]->view(), E[2]->view()};
+            if (m_be->apply_silver_mueller(Ev, Bv, dt[0], m_ctx.dinv.data(), m_dom_lo, m_dom_hi, m_sm_lo, m_sm_hi, m_ctx.stream) != 0)
+                throw std::runtime_error("apply_silver_mueller failed");
+        }
     }
 
     // Source/Parallelization/WarpXComm.cpp:644-660,699-827 -> ablastr FillBoundary (Communication.cpp:71-115)
@@ -861,10 +882,12 @@ public:
         m_be->stream_sync(m_ctx.stream);
     }
     int sort_intervals = -1;         // Source/WarpX.cpp:1335 (GPU default 4; set by the config)
-    // WarpX::field_boundary_lo / field_boundary_hi restricted to periodic | PEC
+    // WarpX::field_boundary_lo / field_boundary_hi restricted to periodic | PEC | Silver-Mueller
     int32_t m_pec_lo[3] = {0, 0, 0}, m_pec_hi[3] = {0, 0, 0}, m_dom_lo[3] = {0, 0, 0}, m_dom_hi[3] = {0, 0, 0};
-    bool m_any_pec = false;    // the domain has a PEC wall (schedule decisions: identical on every brick)
-    bool m_pec_here = false;   // ... and this brick touches one
+    int32_t m_sm_lo[3] = {0, 0, 0}, m_sm_hi[3] = {0, 0, 0};
+    bool m_any_wall = false;   // the domain has a non-periodic face (schedule decisions: identical on every brick)
+    bool m_pec_here = false;   // this brick touches a PEC wall
+    bool m_sm_here = false;    // this brick touches a Silver-Mueller face
     bool m_any_reflecting_wall = false;
     // WarpX::do_moving_window, moving_window_dir, moving_window_v (m/s), moving_window_x
     bool do_moving_window = false;

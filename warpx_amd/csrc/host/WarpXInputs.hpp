@@ -360,7 +360,9 @@ inline std::unique_ptr<SimHandle> sim_from_inputs(const Backend* be, const std::
             std::transform(b.begin(), b.end(), b.begin(), [](unsigned char c) { return (char)std::tolower(c); });
             if (b == "periodic") out[d] = WXA_BOUNDARY_PERIODIC;
             else if (b == "pec") out[d] = WXA_BOUNDARY_PEC;
-            else throw std::runtime_error("inputs: field boundary '" + words[d] + "' is not on this path (periodic, pec)");
+            else if (b == "absorbing_silver_mueller") out[d] = WXA_BOUNDARY_SILVER_MUELLER;
+            else throw std::runtime_error("inputs: field boundary '" + words[d] +
+                                          "' is not on this path (periodic, pec, absorbing_silver_mueller)");
         }
     };
     field_bc("boundary.field_lo", cfg.field_boundary_lo);

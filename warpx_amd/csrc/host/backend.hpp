@@ -65,6 +65,11 @@ struct Backend {
                        const int32_t* pec_hi, void*);
     int (*apply_pec_rho)(const wxa_field_view*, const int32_t* dom_lo, const int32_t* dom_hi, const int32_t* pec_lo,
                          const int32_t* pec_hi, void*);
+    // optional: Silver-Mueller absorbing field boundary (wxa_apply_silver_mueller); a simulation that asks for it on a
+    // backend without the entry is refused at construction
+    int (*apply_silver_mueller)(const wxa_field_view* E, const wxa_field_view* B, double dt, const double* dinv,
+                                const int32_t* dom_lo, const int32_t* dom_hi, const int32_t* sm_lo, const int32_t* sm_hi,
+                                void*) = nullptr;
     // moving window field shift (scratch: a second array of the same shape) and the laser antenna push
     int (*shift_field_window)(const wxa_field_view*, double* tmp, int32_t dir, int32_t num_shift, const int* periodic,
                               void*);

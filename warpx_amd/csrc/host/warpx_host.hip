@@ -164,6 +164,9 @@ const Backend* hip_backend() {
                            const int32_t* phi, void* st) -> int { return wxa_apply_pec_j(J, dlo, dhi, plo, phi, st); };
         b.apply_pec_rho = [](const wxa_field_view* r, const int32_t* dlo, const int32_t* dhi, const int32_t* plo,
                              const int32_t* phi, void* st) -> int { return wxa_apply_pec_rho(r, dlo, dhi, plo, phi, st); };
+        b.apply_silver_mueller = [](const wxa_field_view* E, const wxa_field_view* B, double dt, const double* dinv,
+                                    const int32_t* dlo, const int32_t* dhi, const int32_t* slo, const int32_t* shi,
+                                    void* st) -> int { return wxa_apply_silver_mueller(E, B, dt, dinv, dlo, dhi, slo, shi, st); };
         b.deposit_charge = [](const wxa_particle_view* p, const wxa_field_view* r, const wxa_grid_geom* g, double q,
                               int order, void* st) -> int { return wxa_deposit_charge(p, r, g, q, order, st); };
         b.shift_field_window = [](const wxa_field_view* f, double* tmp, int32_t dir, int32_t n, const int* per,

@@ -33,7 +33,7 @@ class WarpXSim:
             cfg.prob_hi[d] = float(prob_hi[d])
             cfg.nbricks[d] = int(nbricks[d])
             cfg.coord[d] = int(coord[d])
-            cfg.field_boundary_lo[d] = int(field_boundary_lo[d])   # _capi.BOUNDARY_PERIODIC / BOUNDARY_PEC
+            cfg.field_boundary_lo[d] = int(field_boundary_lo[d])   # _capi.BOUNDARY_PERIODIC / BOUNDARY_PEC / BOUNDARY_SILVER_MUELLER
             cfg.field_boundary_hi[d] = int(field_boundary_hi[d])
             cfg.particle_boundary_lo[d] = int(particle_boundary_lo[d])   # _capi.PBOUNDARY_*
             cfg.particle_boundary_hi[d] = int(particle_boundary_hi[d])
