@@ -603,8 +603,9 @@ typedef struct wxa_moving_window {
     double  v;       /* in units of c (> 0: towards +dir) */
 } wxa_moving_window;
 
-/* <species>.injection_style = NUniformPerCell with a constant density, at rest, inside
- * [lo, hi) (xmin..zmax), <species>.do_continuous_injection = 1
+/* <species>.injection_style = NUniformPerCell, inside
+ * [lo, hi) (xmin..zmax), <species>.do_continuous_injection = 1; the density is the constant below
+ * (profile = constant, wxa_add_plasma) or an expression (wxa_add_plasma_profile)
  * (PhysicalParticleContainer::AddPlasma, Source/Particles/PhysicalParticleContainer.cpp:924-1333;
  * ContinuousInjection :2518-2528) */
 typedef struct wxa_plasma_injector {
@@ -641,6 +642,51 @@ wxa_status wxa_add_plasma(const wxa_particle_view* dst, const wxa_plasma_injecto
                           const double brick_lo[3], const double brick_hi[3],
                           const wxa_injected_momentum* momentum,
                           int64_t* n_added, wxa_workspace* ws, void* stream);
+
+/* ---- expressions on the device: density profiles and momenta of an injector --------------------------------
+ * An expression of the decks' grammar (wxa_parser_eval; amrex::Parser in the reference) compiled once into a postfix
+ * program: `vars` are bound at evaluation time in this order, the named constants are folded in now.  An unknown name or
+ * a syntax error is WXA_ERR_INVALID_ARG with the parser's message. */
+typedef struct wxa_expr wxa_expr;
+wxa_status wxa_expr_compile(const char* text, const char* const* var_names, int32_t nvars,
+                            const char* const* const_names, const double* const_values, int32_t nconst,
+                            wxa_expr** out);
+void       wxa_expr_destroy(wxa_expr* e);
+/* <species>.profile = predefined as such a program of (x, y, z): predefined_profile_name = parabolic_channel with the six
+ * predefined_profile_params z_start ramp_up plateau ramp_down rc n0 (InjectorDensity.H:82-107), written down op by op
+ * in the reference's operation order.  Other names and parameter counts are refused by name. */
+wxa_status wxa_expr_predefined(const char* profile_name, const double* params, int32_t nparams, wxa_expr** out);
+/* operations of the program and the deepest its value stack gets (either may be NULL) */
+wxa_status wxa_expr_info(const wxa_expr* e, int32_t* num_ops, int32_t* depth);
+/* the value for vals[0 .. nvars) on the host (the evaluator the decks' constants go through) */
+wxa_status wxa_expr_eval_host(const wxa_expr* e, const double* vals, double* out);
+/* out[i] = the value at point i of n, variable v of point i at vals[v * n + i]; vals and out are device memory.  The
+ * device runs the host's program with the host's semantics, one rounding per operation: arithmetic, comparisons, sqrt,
+ * abs, floor, ceil, min, max, fmod, heaviside, if and integer powers give the host's bits, the transcendental functions
+ * differ from libm by ulps.  Programs of more than 256 operations or a value stack deeper than 16 are refused
+ * (WXA_ERR_INVALID_ARG, with the measured figure). */
+wxa_status wxa_expr_eval_device(wxa_expr* e, const double* vals, int64_t n, double* out, void* stream);
+/* The density (x, y, z) -> m^-3 and, optionally (NULL = none), the three momenta (x, y, z) -> gamma beta of the injector
+ * whose plasma wxa_add_plasma_profile adds through workspace `ws`: checked against the limits above and uploaded to
+ * device memory owned by the workspace, once.  The expressions must outlive their use. */
+wxa_status wxa_workspace_set_injection_profile(wxa_workspace* ws, const wxa_expr* density,
+                                               const wxa_expr* const* momentum);
+/* wxa_add_plasma with <species>.profile = parse_density_function / predefined and, optionally,
+ * momentum_distribution_type = parse_momentum_function (InjectorDensityParser / InjectorDensityPredefined,
+ * InjectorMomentumParser; PhysicalParticleContainer.cpp:1015-1051, :1175-1276): inj->density is not read.
+ * A cell emits particles only if one of its 27 points {lo, mid, hi}^3 (z ballistically corrected) lies inside the
+ * bounds with a density > 0 (:1032-1048).  Lab frame: z0 = applyBallisticCorrection(pos) with the bulk momentum at pos,
+ * bounds, momentum and density at (x, y, z0).  Boosted frame: density at (x, y, z0_lab), momentum at (x, y, 0), then the
+ * Lorentz transform of both.  A particle is dropped where the density < density_min and carries
+ * min(density, density_max) dV / ppc.  `momentum` (constant / gaussian) and `momentum_exprs` exclude each other; both
+ * NULL = at rest.  Expressions other than the ones set on `ws` are set first (an upload).  Everything else as
+ * wxa_add_plasma. */
+wxa_status wxa_add_plasma_profile(const wxa_particle_view* dst, const wxa_plasma_injector* inj,
+                                  const double corner[3], const int32_t ncells[3], const double dx[3],
+                                  const double brick_lo[3], const double brick_hi[3],
+                                  const wxa_injected_momentum* momentum, const wxa_expr* density,
+                                  const wxa_expr* const* momentum_exprs, double density_min, double density_max,
+                                  int64_t* n_added, wxa_workspace* ws, void* stream);
 
 /* lasers.names / <laser>.profile = Gaussian (Source/Particles/LaserParticleContainer.cpp,
  * Source/Laser/LaserProfilesImpl/LaserProfileGaussian.cpp), lab frame, no space-time couplings */
@@ -760,12 +806,22 @@ wxa_status wxa_sim_set_deposit_accumulator(wxa_sim* s, int32_t id, int32_t accum
 /* <species>.do_classical_radiation_reaction (PhysicalParticleContainer.cpp:330-340; PushSelector.H:60-87: the species is
  * pushed by UpdateMomentumBorisWithRadiationReaction whatever algo.particle_pusher says) */
 wxa_status wxa_sim_set_radiation_reaction(wxa_sim* s, int32_t id, int32_t on);
+/* <species>.profile = parse_density_function | predefined, density_min, density_max and, with momentum != NULL,
+ * momentum_distribution_type = parse_momentum_function for species `id` (PlasmaInjector.cpp: parseDensity,
+ * parseMomentum; InjectorDensity.H:82-107 for parabolic_channel): `inj` gives ppc and bounds (its density is not read),
+ * the expressions are functions of (x, y, z) and are copied.  On the HIP path they are uploaded here
+ * (wxa_workspace_set_injection_profile; beyond its limits: WXA_ERR_INVALID_ARG, nothing is launched) and parsed momenta
+ * also work in a boosted frame.  add_initial / continuous: fill the domain now / keep injecting behind a moving window. */
+wxa_status wxa_sim_set_injection_profile(wxa_sim* s, int32_t id, const wxa_plasma_injector* inj, const wxa_expr* density,
+                                         const wxa_expr* const* momentum, double density_min, double density_max,
+                                         int32_t add_initial, int32_t continuous);
 /* ---- input-deck front end -------------------------------------------------
  * Builds the simulation a WarpX inputs file describes (amrex::ParmParse syntax, FILE includes,
  * my_constants, math expressions; WarpX::ReadParameters' defaults) for the parameters on this path:
  * 3-D Cartesian, Yee, periodic / PEC field and periodic / absorbing / reflecting particle boundaries,
  * Esirkepov / direct deposition, Boris / Vay, bilinear filter, moving window, species injected as
- * NUniformPerCell (constant density; at rest, constant or parsed momentum; continuous injection),
+ * NUniformPerCell (constant, parsed or predefined parabolic_channel density; at rest, constant, gaussian or
+ * parsed momentum; continuous injection),
  * SingleParticle, MultipleParticles, Gaussian laser antennas, E/B initialised by constants or parsed
  * functions.  Any other parameter that is not plain output / AMReX box sizing is an error, by name.
  * overrides: "name=value" strings applied after the file, like the reference's command line.

@@ -286,6 +286,23 @@ _PRODUCT_SIGS = {
     "field_set_zero_multi": (C.c_int, [_PFV, C.c_int32, C.c_void_p]),
     # E, B, dt, dinv, dom_lo, dom_hi, sm_lo, sm_hi, stream (the oracle has no Silver-Mueller boundary)
     "apply_silver_mueller": (C.c_int, [_FV3, _FV3, C.c_double, _D3, _I32_3, _I32_3, _I32_3, _I32_3, C.c_void_p]),
+    # expressions run by the device, the injector that uses them (the oracle has neither; the CPU build of the host
+    # layer evaluates the expressions in its host loop)
+    "expr_compile": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
+                               C.c_int32, C.POINTER(C.c_void_p)]),
+    "expr_predefined": (C.c_int, [C.c_char_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_void_p)]),
+    "expr_destroy": (None, [C.c_void_p]),
+    "expr_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "expr_eval_host": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "expr_eval_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "workspace_set_injection_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    # dst, inj, corner, ncells, dx, brick_lo, brick_hi, momentum, density, momentum_exprs, density_min, density_max,
+    # n_added, ws, stream
+    "add_plasma_profile": (C.c_int, [_PPV, C.POINTER(PlasmaInjector), _D3, _I32_3, _D3, _D3, _D3,
+                                     C.POINTER(InjectedMomentum), C.c_void_p, C.POINTER(C.c_void_p), C.c_double,
+                                     C.c_double, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    "sim_set_injection_profile": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(PlasmaInjector), C.c_void_p,
+                                            C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int32, C.c_int32]),
     "copy_to_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "copy_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "device_synchronize": (C.c_int, []),
@@ -334,6 +351,53 @@ _ORACLE_SIGS = {
 
 class WxaError(RuntimeError):
     pass
+
+
+class Expr:
+    """A compiled expression of the decks' grammar (wxa_expr): `variables` are bound at evaluation time, `constants`
+    (name -> value) are folded in now.  Needs a library with the expr_* entries (the HIP library)."""
+
+    def __init__(self, lib: "CLib", text: str, variables=("x", "y", "z"), constants=None):
+        constants = dict(constants or {})
+        names = (C.c_char_p * max(1, len(variables)))(*[v.encode() for v in variables])
+        cn = (C.c_char_p * max(1, len(constants)))(*[k.encode() for k in constants])
+        cv = (C.c_double * max(1, len(constants)))(*[float(v) for v in constants.values()])
+        self._lib, self._h, self.nvars = lib, C.c_void_p(), len(variables)
+        lib.expr_compile(text.encode(), names, len(variables), cn, cv, len(constants), C.byref(self._h))
+
+    @classmethod
+    def predefined(cls, lib: "CLib", profile_name: str, params):
+        """<species>.profile = predefined (parabolic_channel) as an expression of (x, y, z)"""
+        self = cls.__new__(cls)
+        self._lib, self._h, self.nvars = lib, C.c_void_p(), 3
+        lib.expr_predefined(profile_name.encode(), (C.c_double * max(1, len(params)))(*params), len(params), C.byref(self._h))
+        return self
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    def info(self):
+        """(operations, deepest value stack) of the program"""
+        n, d = C.c_int32(), C.c_int32()
+        self._lib.expr_info(self._h, C.byref(n), C.byref(d))
+        return n.value, d.value
+
+    def eval_host(self, *vals) -> float:
+        out = C.c_double()
+        self._lib.expr_eval_host(self._h, (C.c_double * max(1, len(vals)))(*vals), C.byref(out))
+        return out.value
+
+    def close(self):
+        if self._h:
+            self._lib._expr_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # noqa: BLE001 -- interpreter shutdown
+            pass
 
 
 # int-returning entry points whose result is a value, not a status

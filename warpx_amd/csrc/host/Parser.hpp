@@ -72,11 +72,54 @@ public:
     }
     double eval() const { return eval(nullptr); }
 
-private:
-    enum Code { NUM, VAR, NEG, ADD, SUB, MUL, DIV, POW, LT, GT, LE, GE, EQ, NE, AND, OR, F1, F2, IF };
+    // The compiled program, for evaluators that run it elsewhere (csrc/expr_device.hpp runs it on the device) and for
+    // programs built without a text (Builder below).  F1 / F2 carry the function id in `arg`, VAR the variable's index.
+    enum Code { NUM, VAR, NEG, ADD, SUB, MUL, DIV, POW, LT, GT, LE, GE, EQ, NE, AND, OR, F1, F2, IF, NUM_CODES };
     struct Op { Code code; int arg; double value; };
-    enum F1Id { SQRT, EXP, LOG, LOG10, SIN, COS, TAN, ASIN, ACOS, ATAN, SINH, COSH, TANH, ABS, FLOOR, CEIL, ERF };
-    enum F2Id { FPOW, ATAN2, FMIN, FMAX, FMOD, HEAVISIDE };
+    enum F1Id { SQRT, EXP, LOG, LOG10, SIN, COS, TAN, ASIN, ACOS, ATAN, SINH, COSH, TANH, ABS, FLOOR, CEIL, ERF, NUM_F1 };
+    enum F2Id { FPOW, ATAN2, FMIN, FMAX, FMOD, HEAVISIDE, NUM_F2 };
+    const std::vector<Op>& program() const { return m_prog; }
+    int num_vars() const { return (int)m_vars.size(); }
+    // deepest the value stack gets while the program runs
+    int depth() const {
+        int depth = 0, deepest = 0;
+        for (const Op& op : m_prog) {
+            depth += (op.code == NUM || op.code == VAR) ? 1 : (op.code == NEG || op.code == F1) ? 0 : (op.code == IF) ? -2 : -1;
+            deepest = depth > deepest ? depth : deepest;
+        }
+        return deepest;
+    }
+    // A program written down in postfix order by the caller: the operations run exactly as given, nothing is parsed or
+    // reordered (the predefined density profiles of WarpXInputs.hpp keep the reference's operation order this way).
+    class Builder {
+    public:
+        explicit Builder(const std::vector<std::string>& vars) : m_vars(vars) {}
+        Builder& num(double v) { m_ops.push_back(Op{NUM, 0, v}); return *this; }
+        Builder& var(int i) { m_ops.push_back(Op{VAR, i, 0.0}); return *this; }
+        Builder& op(Code c) { m_ops.push_back(Op{c, 0, 0.0}); return *this; }
+        Builder& f1(F1Id f) { m_ops.push_back(Op{F1, (int)f, 0.0}); return *this; }
+        Builder& f2(F2Id f) { m_ops.push_back(Op{F2, (int)f, 0.0}); return *this; }
+        Parser done() const {
+            Parser m_p;
+            m_p.m_vars = m_vars;
+            m_p.m_prog = m_ops;
+            int depth = 0;
+            for (const Op& o : m_ops) {
+                const int need = (o.code == NUM || o.code == VAR) ? 0 : (o.code == NEG || o.code == F1) ? 1 : (o.code == IF) ? 3 : 2;
+                if (depth < need) throw std::runtime_error("parser: malformed built program");
+                depth += 1 - need;
+                if (o.code == VAR && (o.arg < 0 || o.arg >= (int)m_p.m_vars.size())) throw std::runtime_error("parser: bad variable in a built program");
+            }
+            if (depth != 1 || m_p.depth() > 64) throw std::runtime_error("parser: malformed built program");
+            m_p.m_src = "<built>";
+            return m_p;
+        }
+    private:
+        std::vector<std::string> m_vars;
+        std::vector<Op> m_ops;
+    };
+
+private:
 
     // integer exponents by repeated multiplication, like the reference's parser does for constant integer powers
     static double power(double a, double b) {

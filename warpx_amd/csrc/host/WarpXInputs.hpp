@@ -220,6 +220,50 @@ inline void beam_normals(uint64_t stream, uint64_t index, double n[6]) {
     }
 }
 
+// InjectorDensityPredefined, parabolic_channel (Source/Initialization/InjectorDensity.H:82-107) as a program written
+// down op by op in the reference's operation order (a text would go through the grammar's own association):
+//   n(z) = ramp_up: 0.5 (1 - cos(pi (z - z_start) / ramp_up)), plateau: 1, ramp_down: 0.5 (1 + cos(pi (z - z_start -
+//   ramp_up - plateau) / ramp_down)), else 0;  n *= n0 (1 + 4 (x x + y y) / (kp kp rc rc rc rc))
+// p = z_start ramp_up plateau ramp_down rc n0.  The branches are selects: every arm is evaluated and finite or unused.
+inline Parser parabolic_channel_program(const double p[6], const std::map<std::string, double>& k) {
+    using P = Parser;
+    const double z_start = p[0], ramp_up = p[1], plateau = p[2], ramp_down = p[3], rc = p[4], n0 = p[5];
+    const double kp = k.at("q_e") / k.at("clight") * std::sqrt(n0 / (k.at("m_e") * k.at("epsilon0")));
+    const double pi = 3.14159265358979323846;   // MathConst::pi
+    P::Builder b({"x", "y", "z"});
+    auto zs = [&]() { b.var(2).num(z_start).op(P::SUB); };
+    auto between = [&](double lo, double hi) {   // (z - z_start) >= lo and (z - z_start) < hi
+        zs(); b.num(lo).op(P::GE); zs(); b.num(hi).op(P::LT).op(P::AND);
+    };
+    between(0.0, ramp_up);
+    b.num(0.5).num(1.); b.num(pi); zs(); b.op(P::MUL).num(ramp_up).op(P::DIV).f1(P::COS).op(P::SUB).op(P::MUL);
+    between(ramp_up, ramp_up + plateau);
+    b.num(1.);
+    between(ramp_up + plateau, ramp_up + plateau + ramp_down);
+    b.num(0.5).num(1.); b.num(pi); zs(); b.num(ramp_up).op(P::SUB).num(plateau).op(P::SUB).op(P::MUL).num(ramp_down).op(P::DIV)
+        .f1(P::COS).op(P::ADD).op(P::MUL);
+    b.num(0.).op(P::IF).op(P::IF).op(P::IF);
+    b.num(n0).num(1.).num(4.).var(0).var(0).op(P::MUL).var(1).var(1).op(P::MUL).op(P::ADD).op(P::MUL)
+        .num(kp * kp * rc * rc * rc * rc).op(P::DIV).op(P::ADD).op(P::MUL);
+    b.op(P::MUL);
+    return b.done();
+}
+
+// <species>.predefined_profile_name / predefined_profile_params (InjectorDensityPredefined's constructor): the name as
+// the deck gives it, case and '_' / '-' ignored.  `who` starts the message of a refusal.
+inline Parser predefined_density_program(const std::string& who, const std::string& profile_name, const double* params,
+                                         int nparams, const std::map<std::string, double>& k) {
+    std::string w;
+    for (char c : profile_name)
+        if (c != '-' && c != '_') w.push_back((char)std::tolower((unsigned char)c));
+    if (w != "parabolicchannel")
+        throw std::runtime_error(who + ": predefined_profile_name = " + profile_name + " is not on this path (parabolic_channel)");
+    if (nparams != 6)
+        throw std::runtime_error(who + ": predefined_profile_params: parabolic_channel takes 6 values (z_start ramp_up "
+                                 "plateau ramp_down rc n0), got " + std::to_string(nparams));
+    return parabolic_channel_program(params, k);
+}
+
 inline int axis_of(const std::string& w, const std::string& key) {
     if (w == "x") return 0;
     if (w == "y") return 1;
@@ -664,9 +708,35 @@ inline std::unique_ptr<SimHandle> sim_from_inputs(const Backend* be, const std::
                 pp.queryWithParser(name + lo_keys[d], inj.lo[d]);
                 pp.queryWithParser(name + hi_keys[d], inj.hi[d]);
             }
-            if (!pp.query_word(name + ".profile", w) || w != "constant")
-                throw std::runtime_error("inputs: " + name + ".profile must be constant on this path");
-            inj.density = pp.getWithParser(name + ".density");
+            // PlasmaInjector::parseDensity (PlasmaInjector.cpp): constant, parse_density_function, predefined
+            if (!pp.query_word(name + ".profile", w)) throw std::runtime_error("inputs: " + name + ".profile must be set");
+            if (w == "constant") {
+                inj.density = pp.getWithParser(name + ".density");
+            } else if (w == "parsedensityfunction" || w == "predefined") {
+                Parser dens;
+                if (w == "parsedensityfunction") {
+                    const std::string key = name + ".density_function(x,y,z)";
+                    std::string expr;
+                    if (!pp.query(key, expr)) throw std::runtime_error("inputs: " + key + " must be set");
+                    dens = pp.makeParser(expr, {"x", "y", "z"});
+                } else {
+                    pp.ignore(name + ".density_function(x,y,z)");   // read by parse_density_function only, as in the reference
+                    std::string which;
+                    if (!pp.query(name + ".predefined_profile_name", which))
+                        throw std::runtime_error("inputs: " + name + ".predefined_profile_name must be set");
+                    std::vector<double> prm;
+                    if (!pp.queryArrWithParser(name + ".predefined_profile_params", prm))
+                        throw std::runtime_error("inputs: " + name + ".predefined_profile_params must be set");
+                    dens = predefined_density_program("inputs: " + name, which, prm.data(), (int)prm.size(), pp.constants());
+                }
+                double dmin = 0.0, dmax = std::numeric_limits<double>::max();   // PlasmaInjector.cpp: density_min / density_max
+                pp.queryWithParser(name + ".density_min", dmin);
+                pp.queryWithParser(name + ".density_max", dmax);
+                pc->SetDensityFunction(dens, dmin, dmax);
+            } else {
+                throw std::runtime_error("inputs: " + name + ".profile = " + w +
+                                         " is not on this path (constant, parse_density_function, predefined)");
+            }
             std::string mom = "atrest";
             pp.query_word(name + ".momentum_distribution_type", mom);
             if (mom == "constant") {
@@ -684,10 +754,7 @@ inline std::unique_ptr<SimHandle> sim_from_inputs(const Backend* be, const std::
                     if (!pp.query(key, expr)) throw std::runtime_error("inputs: " + key + " must be set");
                     f[d] = pp.makeParser(expr, {"x", "y", "z"});
                 }
-                pc->SetMomentumFunction([f0 = f[0], f1 = f[1], f2 = f[2]](double x, double y, double z, double* out) {
-                    const double xyz[3] = {x, y, z};
-                    out[0] = f0.eval(xyz); out[1] = f1.eval(xyz); out[2] = f2.eval(xyz);
-                });
+                pc->SetMomentumFunctions(f);
             } else if (mom == "gaussian") {
                 // InjectorMomentumGaussian: u = u_m + u_th N(0,1) per component.  The reference draws from
                 // AMReX's generator, which no other program reproduces; here a counter-based stream keyed by

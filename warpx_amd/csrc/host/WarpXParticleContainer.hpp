@@ -13,9 +13,11 @@
 #include <cstdio>
 #include <functional>
 #include <limits>
+#include <memory>
 #include <cstdlib>
 
 #include "BrickComm.hpp"
+#include "ExprHandle.hpp"
 #include "BTDiagnostics.hpp"
 
 namespace wxa::host {
@@ -585,13 +587,15 @@ class PhysicalParticleContainer : public WarpXParticleContainer {
 public:
     using WarpXParticleContainer::WarpXParticleContainer;
 
-    // <species>.injection_style = NUniformPerCell, profile = constant, momentum at_rest
+    // <species>.injection_style = NUniformPerCell: ppc and bounds; the density is inj.density (profile = constant) unless
+    // SetDensityFunction gave one.  On a backend with add_plasma_profile the expressions are uploaded here.
     void SetPlasmaInjector(const wxa_plasma_injector& inj, bool continuous) {
         if (inj.ppc[0] < 1 || inj.ppc[1] < 1 || inj.ppc[2] < 1 || !(inj.density >= 0.0))
             throw std::runtime_error("plasma injector: bad density or particles per cell");
         m_inj = inj;
         m_has_injector = true;
         m_do_continuous_injection = continuous;
+        UploadInjectionPrograms();
     }
     bool doContinuousInjection() const override { return m_has_injector && m_do_continuous_injection; }
     // PhysicalParticleContainer::ContinuousInjection (PhysicalParticleContainer.cpp:2518-2528)
@@ -606,10 +610,11 @@ public:
         return u[dir];
     }
 
-    // PhysicalParticleContainer::AddPlasma (:924-1333) for one box per brick, lab frame, plasma at rest: the
-    // cells of part_box that overlap this brick (find_overlap, Source/Particles/AddPlasmaUtilities.cpp:12-43),
-    // positions from InjectorPositionRegular, weight = density * cell volume / particles per cell.
-    // Generated on the host (a slab of one or two cell layers per step in a moving window) and appended.
+    // PhysicalParticleContainer::AddPlasma (:924-1333) for one box per brick: the cells of part_box that overlap this
+    // brick (find_overlap, Source/Particles/AddPlasmaUtilities.cpp:12-43), positions from InjectorPositionRegular,
+    // weight = density * cell volume / particles per cell; the density is the injector's constant or a function of the
+    // position (SetDensityFunction).  On the device where the backend has the entry (add_plasma for the constant,
+    // add_plasma_profile for expressions); otherwise generated on the host (lab frame only) and appended.
     void AddPlasma(const double* part_lo, const double* part_hi) {
         if (!m_has_injector) return;
         m_inj.gamma_boost = m_ctx->gamma_boost;
@@ -634,7 +639,26 @@ public:
             nov[d] = (int)std::round((ohi[d] - olo[d]) / dx);
         }
         const int nppc = in.ppc[0] * in.ppc[1] * in.ppc[2];
-        if (m_ctx->be->add_plasma && (!m_momentum || m_momentum_on_device)) {
+        if (ExpressionsOnDevice()) {
+            // density and / or momenta as expressions, evaluated by the device (wxa_add_plasma_profile)
+            const int64_t room = (int64_t)nov[0] * nov[1] * nov[2] * nppc;
+            if (room == 0) return;
+            if (m_programs_dirty) UploadInjectionPrograms();
+            const int64_t n0 = m_tile.numParticles();
+            m_tile.resize(n0 + room);
+            const wxa_particle_view dst = m_tile.view(n0, room);
+            const int32_t nc[3] = {nov[0], nov[1], nov[2]};
+            const wxa_expr* mom[3] = {m_mom_expr[0].get(), m_mom_expr[1].get(), m_mom_expr[2].get()};
+            int64_t added = 0;
+            check_be(m_ctx->be->add_plasma_profile(&dst, &in, olo, nc, m_ctx->dx.data(), m_ctx->brick_plo.data(),
+                                                   m_ctx->brick_phi.data(), m_momentum_on_device ? &m_device_momentum : nullptr,
+                                                   m_density_expr.get(), m_mom_expr[0] ? mom : nullptr, m_density_min,
+                                                   m_density_max, &added, m_ws, m_ctx->stream),
+                     "add_plasma_profile");
+            m_tile.resize(n0 + added);
+            return;
+        }
+        if (m_ctx->be->add_plasma && !m_has_density_function && (!m_momentum || m_momentum_on_device)) {
             // on the device: no host arrays, no copy (a plane of a moving window at 256^2 x 8 ppc is 30 MB)
             const int64_t room = (int64_t)nov[0] * nov[1] * nov[2] * nppc;
             if (room == 0) return;
@@ -650,8 +674,10 @@ public:
             return;
         }
         if (m_ctx->gamma_boost > 1.0)
-            throw std::runtime_error("AddPlasma: a momentum function evaluated on the host is lab-frame only; use at_rest, "
-                                     "constant or gaussian momenta in a boosted frame");
+            throw std::runtime_error("AddPlasma: the host loop (a backend without add_plasma_profile) is lab-frame only");
+        if (m_momentum_on_device)
+            throw std::runtime_error("AddPlasma: gaussian / constant device momenta with a density function need a backend "
+                                     "with add_plasma_profile");
         const double scale_fac = m_ctx->dx[0] * m_ctx->dx[1] * m_ctx->dx[2] / nppc;   // compute_scale_fac_volume
         auto inside = [&](double x, double y, double z) {   // InjectorPosition::insideBounds
             return x < in.hi[0] && x >= in.lo[0] && y < in.hi[1] && y >= in.lo[1] && z < in.hi[2] && z >= in.lo[2];
@@ -674,7 +700,7 @@ public:
                         const int t[3] = {a % 3, (a / 3) % 3, a / 9};
                         double q[3];
                         for (int d = 0; d < 3; ++d) q[d] = t[d] == 0 ? lo[d] : (t[d] == 1 ? (lo[d] + hi[d]) / 2. : hi[d]);
-                        any = inside(q[0], q[1], q[2]) && in.density > 0;
+                        any = inside(q[0], q[1], q[2]) && (m_has_density_function ? m_density.eval(q) : in.density) > 0;
                     }
                     if (!any) continue;
                     for (int ip = 0; ip < nppc; ++ip) {
@@ -691,8 +717,17 @@ public:
                             in_tile = in_tile && pos[d] > m_ctx->brick_plo[d] && pos[d] < m_ctx->brick_phi[d];
                         }
                         if (!in_tile || !inside(pos[0], pos[1], pos[2])) continue;
+                        double dens = in.density;
+                        // :1196-1208, but at pos: this loop applies no ballistic correction (probe, bounds, density and
+                        // momentum all see the lattice point itself), so with a bulk momentum at t > 0 it is not the
+                        // reference's set; the device entries are
+                        if (m_has_density_function) {
+                            dens = m_density.eval(pos);
+                            if (dens < m_density_min) continue;
+                            dens = m_density_max < dens ? m_density_max : dens;
+                        }
                         for (int d = 0; d < 3; ++d) cols[d].push_back(pos[d]);
-                        cols[3].push_back(in.density * scale_fac);
+                        cols[3].push_back(dens * scale_fac);
                         double u[3] = {0.0, 0.0, 0.0};                       // at_rest
                         if (m_momentum) m_momentum(pos[0], pos[1], pos[2], u);   // InjectorMomentum::getMomentum
                         for (int d = 0; d < 3; ++d) cols[4 + d].push_back(u[d] * 299'792'458.);   // :1271-1273
@@ -706,6 +741,33 @@ public:
     void SetMomentumFunction(std::function<void(double, double, double, double*)> f) {   // evaluated on the host
         m_momentum = std::move(f);
         m_momentum_on_device = false;
+        for (auto& e : m_mom_expr) e.reset();   // no programs of an earlier SetMomentumFunctions behind the callback
+        m_programs_dirty = true;
+    }
+    // <species>.momentum_distribution_type = parse_momentum_function as three programs (InjectorMomentumParser): on a
+    // backend with add_plasma_profile they run on the device -- no slab is built on the host, and a boosted frame
+    // works --, otherwise in the host loop of AddPlasma.  BulkMomentum evaluates them on the host either way.
+    void SetMomentumFunctions(const Parser f[3]) {
+        for (int d = 0; d < 3; ++d)
+            if (f[d].empty() || f[d].num_vars() != 3) throw std::runtime_error("momentum functions: three functions of (x, y, z)");
+        SetMomentumFunction([f0 = f[0], f1 = f[1], f2 = f[2]](double x, double y, double z, double* out) {
+            const double xyz[3] = {x, y, z};
+            out[0] = f0.eval(xyz); out[1] = f1.eval(xyz); out[2] = f2.eval(xyz);
+        });
+        if (m_ctx->be->add_plasma_profile)
+            for (int d = 0; d < 3; ++d) m_mom_expr[d] = std::make_unique<wxa_expr>(f[d]);
+        m_programs_dirty = true;
+    }
+    // <species>.profile = parse_density_function | predefined (InjectorDensityParser / InjectorDensityPredefined) with
+    // <species>.density_min / density_max (PlasmaInjector.cpp: 0 and the largest double when unset)
+    void SetDensityFunction(const Parser& f, double density_min, double density_max) {
+        if (f.empty() || f.num_vars() != 3) throw std::runtime_error("density function: a function of (x, y, z)");
+        m_density = f;
+        m_has_density_function = true;
+        m_density_min = density_min;
+        m_density_max = density_max;
+        if (m_ctx->be->add_plasma_profile) m_density_expr = std::make_unique<wxa_expr>(f);
+        m_programs_dirty = true;
     }
     // InjectorMomentumConstant (u_th = 0) / InjectorMomentumGaussian: drawn on the device (wxa_add_plasma)
     void SetGaussianMomentum(const double u_mean[3], const double u_th[3], uint64_t seed) {
@@ -717,6 +779,31 @@ public:
         m_device_momentum.seed = seed;
         m_momentum = [](double, double, double, double*) { throw std::runtime_error("AddPlasma: no backend entry for the injection"); };
         m_momentum_on_device = true;
+        for (auto& e : m_mom_expr) e.reset();
+        m_programs_dirty = true;
+    }
+
+private:
+    // the device evaluates the injector's expressions: a density function or parsed momenta on a backend that has the entry
+    bool ExpressionsOnDevice() const {
+        return m_ctx->be->add_plasma_profile && (m_has_density_function || m_mom_expr[0]);
+    }
+    void check_be(int rc, const char* what) const {
+        if (rc == 0) return;
+        const char* why = m_ctx->be->last_error ? m_ctx->be->last_error() : nullptr;
+        throw std::runtime_error(std::string(what) + " returned status " + std::to_string(rc) + (why ? std::string(": ") + why : ""));
+    }
+    // the programs go to the device once, when the injector is set (wxa_workspace_set_injection_profile checks the
+    // evaluator's limits there); parsed momenta over a constant density get the density as a one-operation program
+    void UploadInjectionPrograms() {
+        if (!m_has_injector || !ExpressionsOnDevice()) return;
+        if (!m_has_density_function)
+            m_density_expr = std::make_unique<wxa_expr>(Parser::Builder({"x", "y", "z"}).num(m_inj.density).done());
+        const wxa_expr* mom[3] = {m_mom_expr[0].get(), m_mom_expr[1].get(), m_mom_expr[2].get()};
+        if (m_ctx->be->ws_set_injection_profile)
+            check_be(m_ctx->be->ws_set_injection_profile(m_ws, m_density_expr.get(), m_mom_expr[0] ? mom : nullptr),
+                     "ws_set_injection_profile");
+        m_programs_dirty = false;
     }
 
 private:
@@ -727,6 +814,10 @@ private:
     bool m_streaming_set = false;
     bool m_momentum_on_device = false;
     wxa_injected_momentum m_device_momentum{};
+    Parser m_density;
+    bool m_has_density_function = false, m_programs_dirty = false;
+    double m_density_min = 0.0, m_density_max = std::numeric_limits<double>::max();
+    std::unique_ptr<wxa_expr> m_density_expr, m_mom_expr[3];   // what the backend's add_plasma_profile takes
 
 public:
 

@@ -15,6 +15,8 @@
 
 #include "../../../include/warpx_amd.h"
 
+struct wxa_expr;   // ExprHandle.hpp
+
 namespace wxa::host {
 
 struct Backend {
@@ -49,11 +51,21 @@ struct Backend {
                             const wxa_grid_geom*, double, double, double, int, int, int, void* ws, int part, void*);
     int (*deposit_current)(const wxa_particle_view*, const wxa_field_view*, const wxa_grid_geom*, double,
                            double, double, int, int, void* ws, void*);
-    // PhysicalParticleContainer::AddPlasma on the device (constant density; at rest, constant or gaussian momentum)
+    // PhysicalParticleContainer::AddPlasma on the device (profile = constant; at rest, constant or gaussian momentum)
     int (*add_plasma)(const wxa_particle_view* dst, const wxa_plasma_injector*, const double* corner, const int32_t* ncells,
                       const double* dx, const double* brick_lo, const double* brick_hi, const wxa_injected_momentum* momentum,
                       int64_t* n_added,
                       void* ws, void*);
+    // optional: the same with the density and / or the momenta as expressions run by the device (wxa_add_plasma_profile,
+    // wxa_workspace_set_injection_profile); without them AddPlasma evaluates the expressions in its host loop
+    int (*add_plasma_profile)(const wxa_particle_view* dst, const wxa_plasma_injector*, const double* corner,
+                              const int32_t* ncells, const double* dx, const double* brick_lo, const double* brick_hi,
+                              const wxa_injected_momentum* momentum, const wxa_expr* density,
+                              const wxa_expr* const* momentum_exprs, double density_min, double density_max,
+                              int64_t* n_added, void* ws, void*) = nullptr;
+    int (*ws_set_injection_profile)(void* ws, const wxa_expr* density, const wxa_expr* const* momentum) = nullptr;
+    // optional: the message behind the last non-zero status of an entry
+    const char* (*last_error)() = nullptr;
     // diagnostics: doChargeDepositionShapeN
     int (*deposit_charge)(const wxa_particle_view*, const wxa_field_view*, const wxa_grid_geom*, double, int, void*);
     // PEC field boundary (wxa_apply_pec_e / wxa_apply_pec_b)

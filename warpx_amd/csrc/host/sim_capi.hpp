@@ -125,6 +125,36 @@ inline int sim_set_injection(SimHandle* h, int32_t id, const wxa_plasma_injector
     }
 }
 
+// the same with <species>.profile = parse_density_function | predefined (density, density_min, density_max) and,
+// with momentum != nullptr, momentum_distribution_type = parse_momentum_function
+inline int sim_set_injection_profile(SimHandle* h, int32_t id, const wxa_plasma_injector* inj, const wxa_expr* density,
+                                     const wxa_expr* const* momentum, double density_min, double density_max,
+                                     int add_initial, int continuous) {
+    if (!h || !inj || !density || id < 0 || id >= h->warpx->GetPartContainer().nSpecies()) return WXA_ERR_INVALID_ARG;
+    try {
+        WarpX& w = *h->warpx;
+        auto* pc = dynamic_cast<PhysicalParticleContainer*>(&w.GetPartContainer().GetParticleContainer(id));
+        if (!pc) return WXA_ERR_INVALID_ARG;
+        if (momentum) {
+            if (!momentum[0] || !momentum[1] || !momentum[2]) throw std::runtime_error("set_injection_profile: three momentum expressions");
+            const Parser f[3] = {momentum[0]->parser, momentum[1]->parser, momentum[2]->parser};
+            pc->SetMomentumFunctions(f);
+        }
+        pc->SetDensityFunction(density->parser, density_min, density_max);
+        wxa_plasma_injector in = *inj;
+        in.density = 0.0;
+        pc->SetPlasmaInjector(in, continuous != 0);
+        if (add_initial) {
+            pc->AddPlasma(w.context().prob_lo.data(), w.context().prob_hi.data());
+            if (w.sort_intervals > 0 && pc->TotalNumberOfParticles() > 0) pc->SortParticlesByBin(amrex::IntVect(1));
+        }
+        return WXA_OK;
+    } catch (const std::exception& e) {
+        h->error = e.what();
+        return WXA_ERR_INVALID_ARG;
+    }
+}
+
 inline int sim_add_laser(SimHandle* h, const wxa_laser_antenna* la) {
     if (!h || !la) return WXA_ERR_INVALID_ARG;
     try {
@@ -338,6 +368,16 @@ inline int sim_get_timers(SimHandle* h, double ms[8], int64_t counts[8], int res
                                int continuous) {                                                       \
         return (RET)wxa::host::sim_set_injection(reinterpret_cast<wxa::host::SimHandle*>(s), id, inj,    \
                                                  add_initial, continuous);                             \
+    }                                                                                                  \
+    RET PFX##sim_set_injection_profile(SIMTYPE* s, int32_t id, const wxa_plasma_injector* inj,         \
+                                       const wxa_expr* density, const wxa_expr* const* momentum,       \
+                                       double density_min, double density_max, int32_t add_initial,    \
+                                       int32_t continuous) {                                           \
+        auto* h = reinterpret_cast<wxa::host::SimHandle*>(s);                                          \
+        int rc = wxa::host::sim_set_injection_profile(h, id, inj, density, momentum, density_min,      \
+                                                      density_max, add_initial, continuous);           \
+        if (rc != 0 && h) SET_ERROR(h->error.c_str());                                                 \
+        return (RET)rc;                                                                                \
     }                                                                                                  \
     RET PFX##sim_set_external_particle_fields(SIMTYPE* s, int32_t id, const double E[3], const double B[3]) { \
         return (RET)wxa::host::sim_set_external_particle_fields(reinterpret_cast<wxa::host::SimHandle*>(s), id, E, B); \

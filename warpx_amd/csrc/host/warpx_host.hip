@@ -99,6 +99,15 @@ const Backend* hip_backend() {
                           const int32_t* nc, const double* dx, const double* blo, const double* bhi,
                           const wxa_injected_momentum* u, int64_t* n, void* ws, void* st) -> int {
             return wxa_add_plasma(dst, inj, corner, nc, dx, blo, bhi, u, n, static_cast<wxa_workspace*>(ws), st); };
+        b.add_plasma_profile = [](const wxa_particle_view* dst, const wxa_plasma_injector* inj, const double* corner,
+                                  const int32_t* nc, const double* dx, const double* blo, const double* bhi,
+                                  const wxa_injected_momentum* u, const wxa_expr* dens, const wxa_expr* const* mom,
+                                  double dmin, double dmax, int64_t* n, void* ws, void* st) -> int {
+            return wxa_add_plasma_profile(dst, inj, corner, nc, dx, blo, bhi, u, dens, mom, dmin, dmax, n,
+                                          static_cast<wxa_workspace*>(ws), st); };
+        b.ws_set_injection_profile = [](void* ws, const wxa_expr* dens, const wxa_expr* const* mom) -> int {
+            return wxa_workspace_set_injection_profile(static_cast<wxa_workspace*>(ws), dens, mom); };
+        b.last_error = wxa_last_error;
         b.deposit_current = k_deposit;
         b.filter_bilinear = [](const wxa_field_view* s, const wxa_field_view* d, void* st) -> int {
             return wxa_filter_bilinear(s, d, st); };
@@ -227,6 +236,24 @@ extern "C" wxa_status wxa_nci_godfrey_stencil(double cdtodz, int32_t nodal_gathe
                                   cdtodz, nodal_gather != 0);
     f.ComputeStencils();
     for (int i = 0; i < 5; ++i) stencil_z[i] = f.stencil_z[i];
+    return WXA_OK;
+}
+
+// InjectorDensityPredefined as a compiled expression of (x, y, z), built op by op in the reference's operation order
+extern "C" wxa_status wxa_expr_predefined(const char* profile_name, const double* params, int32_t nparams, wxa_expr** out) {
+    if (!profile_name || !out || nparams < 0 || (nparams > 0 && !params)) {
+        wxa::set_last_error("wxa_expr_predefined: bad argument");
+        return WXA_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    try {
+        wxa::host::ParmParse pp;
+        *out = new wxa_expr(wxa::host::inputs_detail::predefined_density_program("wxa_expr_predefined", profile_name, params,
+                                                                                  nparams, pp.constants()));
+    } catch (const std::exception& e) {
+        wxa::set_last_error("%s", e.what());
+        return WXA_ERR_INVALID_ARG;
+    }
     return WXA_OK;
 }
 

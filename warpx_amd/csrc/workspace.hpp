@@ -94,6 +94,12 @@ struct wxa_workspace {
     // the container's plasma streams through the grid (wxa_workspace_set_streaming_plasma): the LDS-tile Esirkepov
     // deposition takes every particle through the wide-frame body inside its loop (deposit_tile.hip, RowsCfg::WL)
     int32_t streaming_plasma = 0;
+    // density and momentum expressions of the container's injector (wxa_workspace_set_injection_profile): the programs
+    // in device memory, uploaded when they are set -- slot 0 the density, 1..3 the momenta; id 0 = none -- and the byte
+    // per cell that the probe pass of wxa_add_plasma_profile leaves for its particle pass
+    wxa::DevBuf inject_prog, inject_mask;
+    uint64_t inject_id[4] = {0, 0, 0, 0};
+    int32_t inject_off[4] = {0, 0, 0, 0}, inject_n[4] = {0, 0, 0, 0};
     // the cell sort folded into PushPX (push_sort.hpp; wxa_push_sort_begin / _end): what is armed for the pushes between
     // begin and end, and the record a COUNT left for the SCATTER of a later push
     struct PushSortState {

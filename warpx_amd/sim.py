@@ -9,6 +9,7 @@ CPU oracle through the same class -- the product never does.
 from __future__ import annotations
 
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -209,6 +210,16 @@ class WarpXSim:
         self.lib.sim_add_species(self._h, float(charge), float(mass), C.byref(v), C.byref(sid))
         self.species.append((float(charge), float(mass)))
         return sid.value
+
+    def set_injection_profile(self, sid: int, injector: _capi.PlasmaInjector, density: _capi.Expr, momentum=None,
+                              density_min=0.0, density_max=sys.float_info.max, add_initial=True, continuous=False):
+        """profile = parse_density_function: `density` (x, y, z) -> m^-3 and, optionally, three `momentum` expressions
+        (x, y, z) -> gamma beta, both run by the device (wxa_sim_set_injection_profile); injector.density is not read"""
+        mom = None
+        if momentum is not None:
+            mom = (C.c_void_p * 3)(*[m.handle for m in momentum])
+        self.lib.sim_set_injection_profile(self._h, sid, C.byref(injector), density.handle, mom, float(density_min),
+                                           float(density_max), int(add_initial), int(continuous))
 
     def set_external_particle_fields(self, sid: int, E, B):
         """particles.E_external_particle / B_external_particle (constant) for species `sid`."""
