@@ -1,10 +1,10 @@
 """Device code of two source trees, compared function by function (no GPU needed):
     python scripts/device_code_diff.py OTHER_TREE [THIS_TREE] > profiles/roundN/device_code_diff.md
-For a change that must leave the device side alone (a host-side refactor).  Emits the gfx950 assembly of the four kernel
+For a change that must leave the device side alone (a host-side refactor).  Emits the gfx950 assembly of the kernel
 files of each tree with the flags tests/test_isa_cpu.py uses, cuts it at the function labels and compares the instruction
 streams.  The order of the functions in a file follows the order of instantiation, and with it the numbers of the block
 labels; a function's own mangled name recurs inside its range and changes where a parameter type is renamed: both are
-normalised, and functions are matched by demangled name without the parameter list.
+normalised, and functions are matched by demangled name without the parameter list, over all the files of a tree.
 Exit status 1 when a function is missing on one side or differs."""
 import os
 import re
@@ -12,7 +12,7 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-FILES = [("fields", ["-ffp-contract=off"]), ("particles", []), ("deposit_tile", []), ("gather_tile", [])]
+FILES = [("fields", ["-ffp-contract=off"]), ("particles", []), ("inject", []), ("deposit_tile", []), ("gather_tile", [])]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "--cuda-device-only", "-S"]
 
 
@@ -64,24 +64,33 @@ def functions(asm):
 def main():
     other = os.path.abspath(sys.argv[1])
     this = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    jobs = [(t, n, e) for n, e in FILES for t in (other, this)]
+    # a tree may lack a file of the list (it was split off later): functions are matched over the union of a tree's files,
+    # so that one that moved compares against itself
+    jobs = [(t, n, e) for n, e in FILES for t in (other, this) if os.path.exists(os.path.join(t, "warpx_amd", "csrc", n + ".hip"))]
     with ThreadPoolExecutor(max_workers=4) as ex:
         asm = list(ex.map(lambda j: functions(assembly(*j)), jobs))
-    bad = 0
+    a, b = {}, {}   # {function: (file, text)}
+    for (t, n, _), fns in zip(jobs, asm):
+        side = a if t == other else b
+        for k, text in fns.items():
+            while k in side:   # the same name in two files
+                k += "'"
+            side[k] = (n, text)
     print("# Device code, function by function\n\n`hipcc " + " ".join(FLAGS) + "` on both trees (scripts/device_code_diff.py): "
-          "compiler output, not a measurement.\n\n| file | functions, other tree | functions, this tree | equal | differ | only in one |\n"
+          "compiler output, not a measurement.\n\n| file, this tree | functions | equal | of those, in another file of the other tree | differ | only in this tree |\n"
           "|---|---|---|---|---|---|")
-    notes = []
-    for i, (name, _) in enumerate(FILES):
-        a, b = asm[2 * i], asm[2 * i + 1]
-        lone = sorted(set(a) ^ set(b))
-        differ = sorted(k for k in set(a) & set(b) if a[k] != b[k])
-        print(f"| {name}.hip | {len(a)} | {len(b)} | {len(set(a) & set(b)) - len(differ)} | {len(differ)} | {len(lone)} |")
-        notes += [f"* {name}.hip differs: `{k}`" for k in differ] + [f"* {name}.hip, only in one tree: `{k}`" for k in lone]
-        bad += len(lone) + len(differ)
+    notes = [f"* only in the other tree ({a[k][0]}.hip): `{k}`" for k in sorted(set(a) - set(b))]
+    for name, _ in FILES:
+        mine = [k for k in b if b[k][0] == name]
+        both = [k for k in mine if k in a]
+        differ = sorted(k for k in both if a[k][1] != b[k][1])
+        moved = [k for k in both if a[k][0] != name and k not in differ]
+        print(f"| {name}.hip | {len(mine)} | {len(both) - len(differ)} | {len(moved)} | {len(differ)} | {len(mine) - len(both)} |")
+        notes += [f"* {name}.hip differs: `{k}`" + (f" (from {a[k][0]}.hip)" if a[k][0] != name else "") for k in differ]
+        notes += [f"* {name}.hip, only in this tree: `{k}`" for k in sorted(set(mine) - set(both))]
     if notes:
         print("\n" + "\n".join(notes))
-    return 1 if bad else 0
+    return 1 if notes else 0
 
 
 if __name__ == "__main__":

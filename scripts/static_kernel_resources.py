@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "warpx_amd", "csrc")
-FILES = [("fields", ["-ffp-contract=off"]), ("deposit_tile", []), ("gather_tile", []), ("particles", [])]
+FILES = [("fields", ["-ffp-contract=off"]), ("deposit_tile", []), ("gather_tile", []), ("particles", []), ("inject", [])]
 
 
 def main():

@@ -31,6 +31,7 @@ SOURCES = [
     ("runtime.hip", []),
     ("fields.hip", ["-ffp-contract=off"]),
     ("particles.hip", []),
+    ("inject.hip", []),
     ("deposit_tile.hip", []),
     ("gather_tile.hip", []),
     ("host/warpx_host.hip", []),

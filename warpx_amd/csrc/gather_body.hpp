@@ -23,6 +23,7 @@ static inline PV make_pv(const wxa_particle_view& p) {
 static inline bool pv_ok(const wxa_particle_view* p) {
     return p && p->np >= 0 && (p->np == 0 || (p->x && p->y && p->z && p->w && p->ux && p->uy && p->uz));
 }
+static inline unsigned blocks_for(long n, int b = 256) { return (unsigned)((n + b - 1) / b); }
 
 template <int O, int G>
 struct GatherShapes {

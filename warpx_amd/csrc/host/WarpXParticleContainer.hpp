@@ -639,37 +639,30 @@ public:
             nov[d] = (int)std::round((ohi[d] - olo[d]) / dx);
         }
         const int nppc = in.ppc[0] * in.ppc[1] * in.ppc[2];
-        if (ExpressionsOnDevice()) {
-            // density and / or momenta as expressions, evaluated by the device (wxa_add_plasma_profile)
-            const int64_t room = (int64_t)nov[0] * nov[1] * nov[2] * nppc;
-            if (room == 0) return;
-            if (m_programs_dirty) UploadInjectionPrograms();
-            const int64_t n0 = m_tile.numParticles();
-            m_tile.resize(n0 + room);
-            const wxa_particle_view dst = m_tile.view(n0, room);
-            const int32_t nc[3] = {nov[0], nov[1], nov[2]};
-            const wxa_expr* mom[3] = {m_mom_expr[0].get(), m_mom_expr[1].get(), m_mom_expr[2].get()};
-            int64_t added = 0;
-            check_be(m_ctx->be->add_plasma_profile(&dst, &in, olo, nc, m_ctx->dx.data(), m_ctx->brick_plo.data(),
-                                                   m_ctx->brick_phi.data(), m_momentum_on_device ? &m_device_momentum : nullptr,
-                                                   m_density_expr.get(), m_mom_expr[0] ? mom : nullptr, m_density_min,
-                                                   m_density_max, &added, m_ws, m_ctx->stream),
-                     "add_plasma_profile");
-            m_tile.resize(n0 + added);
-            return;
-        }
-        if (m_ctx->be->add_plasma && !m_has_density_function && (!m_momentum || m_momentum_on_device)) {
+        const bool expressions = ExpressionsOnDevice();   // density and / or momenta evaluated by the device
+        if (expressions || (m_ctx->be->add_plasma && !m_has_density_function && (!m_momentum || m_momentum_on_device))) {
             // on the device: no host arrays, no copy (a plane of a moving window at 256^2 x 8 ppc is 30 MB)
             const int64_t room = (int64_t)nov[0] * nov[1] * nov[2] * nppc;
             if (room == 0) return;
+            if (expressions && m_programs_dirty) UploadInjectionPrograms();
             const int64_t n0 = m_tile.numParticles();
             m_tile.resize(n0 + room);
             const wxa_particle_view dst = m_tile.view(n0, room);
             const int32_t nc[3] = {nov[0], nov[1], nov[2]};
+            const wxa_injected_momentum* device_mom = m_momentum_on_device ? &m_device_momentum : nullptr;
             int64_t added = 0;
-            check(m_ctx->be->add_plasma(&dst, &in, olo, nc, m_ctx->dx.data(), m_ctx->brick_plo.data(), m_ctx->brick_phi.data(),
-                                        m_momentum_on_device ? &m_device_momentum : nullptr, &added, m_ws, m_ctx->stream),
-                  "add_plasma");
+            if (expressions) {
+                const wxa_expr* mom[3] = {m_mom_expr[0].get(), m_mom_expr[1].get(), m_mom_expr[2].get()};
+                check_be(m_ctx->be->add_plasma_profile(&dst, &in, olo, nc, m_ctx->dx.data(), m_ctx->brick_plo.data(),
+                                                       m_ctx->brick_phi.data(), device_mom, m_density_expr.get(),
+                                                       m_mom_expr[0] ? mom : nullptr, m_density_min, m_density_max, &added,
+                                                       m_ws, m_ctx->stream),
+                         "add_plasma_profile");
+            } else {
+                check(m_ctx->be->add_plasma(&dst, &in, olo, nc, m_ctx->dx.data(), m_ctx->brick_plo.data(),
+                                            m_ctx->brick_phi.data(), device_mom, &added, m_ws, m_ctx->stream),
+                      "add_plasma");
+            }
             m_tile.resize(n0 + added);
             return;
         }
