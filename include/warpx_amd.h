@@ -133,6 +133,15 @@ wxa_status wxa_workspace_set_deposit_accumulator(wxa_workspace* ws, int32_t accu
  * sized for the 1-2 % of a plasma at rest (what overflows that list is deposited with global atomics: 660 ms per launch
  * for the boosted wakefield deck at 256 x 256 x 512 x 8 per cell).  Same sums, another order of additions.  Default 0. */
 wxa_status wxa_workspace_set_streaming_plasma(wxa_workspace* ws, int32_t on);
+/* How many particles the last launch of an LDS-tile kernel through this workspace handed to its straggler pass (global
+ * loads / global atomics) because their stencil left the staged tile: the gather (wxa_gather_push_ws, wxa_gather_push_part)
+ * or the deposition (wxa_deposit_current with a workspace).  0 before the first such launch.  Right after a cell sort the
+ * tile kernels stage every stencil of a particle at rest, so a large count there means the tiles are staged in the wrong
+ * place -- the results stay right (the straggler pass computes the same sums), only the speed goes.  Blocks until the
+ * device is idle: a diagnostic for tests and profiling, not for the step loop. */
+#define WXA_TILE_GATHER  0
+#define WXA_TILE_DEPOSIT 1
+wxa_status wxa_workspace_last_stragglers(wxa_workspace* ws, int32_t tile_kernel, int64_t* count);
 
 const char* wxa_version(void);
 const char* wxa_last_error(void);

@@ -71,6 +71,70 @@ def geom_for(ncell, ng):
     return grid_geom((-LX / 2,) * 3, dx, (0, 0, 0), (ng,) * 3), dx
 
 
+class GeomCase:
+    """One box of a larger index space, as a brick of a multi-brick run or a moving window sees it: `ncell` cells whose
+    first has the global index `box_lo`, in a domain whose index 0 sits at `prob_lo`, cells of `dx`.  geom_for is the
+    special case box_lo = 0, prob_lo = -LX/2, dx = LX / ncell."""
+
+    def __init__(self, ncell, box_lo, prob_lo, dx):
+        self.ncell = tuple(int(v) for v in ncell)
+        self.box_lo = tuple(int(v) for v in box_lo)
+        self.prob_lo = np.asarray(prob_lo, dtype=np.float64)
+        self.dx = np.asarray(dx, dtype=np.float64)
+        self.plo = self.prob_lo + np.asarray(self.box_lo, dtype=np.float64) * self.dx      # the box's lower corner
+        self.phi = self.plo + np.asarray(self.ncell, dtype=np.float64) * self.dx
+        self.dinv = 1.0 / self.dx
+
+    def geom(self, ng):
+        return grid_geom(self.prob_lo, self.dx, self.box_lo, (ng,) * 3)
+
+    def field(self, name, ng, device="cpu", pad=False):
+        return FieldArray(self.ncell, STAG[name], (ng,) * 3, device, lo_valid=self.box_lo, pad=pad)
+
+    def random_fields(self, names, ng, seed, scale=1.0):
+        rng = np.random.default_rng(seed)
+        out = []
+        for name in names:
+            f = self.field(name, ng)
+            out.append(f.from_numpy(rng.standard_normal(f.n) * scale))
+        return out
+
+    def random_particles(self, n, seed, u_scale=0.1):
+        """Positions uniform in the box, momenta gaussian (random_particles for this box)."""
+        rng = np.random.default_rng(seed)
+        pos = [np.minimum(self.plo[d] + (self.phi[d] - self.plo[d]) * rng.random(n), self.below_phi(d)) for d in range(3)]
+        w = 1e9 * (0.5 + rng.random(n))
+        return pos + [w] + [u_scale * plasma.C_LIGHT * rng.standard_normal(n) for _ in range(3)]
+
+    def below_phi(self, d):
+        """The last position inside the box along d."""
+        return np.nextafter(self.phi[d], -np.inf)
+
+    def sort_args(self):
+        """plo, dinv, cell_lo, ncell as wxa_sort_particles_by_cell takes them."""
+        return d3(self.plo), d3(self.dinv), (C.c_int32 * 3)(*self.box_lo), (C.c_int32 * 3)(*self.ncell)
+
+
+def geom_case(ncell, box_lo, prob_lo, dx):
+    return GeomCase(ncell, box_lo, prob_lo, dx)
+
+
+def tile_major_key(pos, plo, dinv, ncell, wrap=(0, 0, 0)):
+    """cell_of (csrc/push_sort.hpp) in numpy, in its own arithmetic (floor((x - plo) * dinv), doubles): the tile-major cell
+    key, indices one period outside brought back where `wrap` says so, clamped otherwise.  Returns (key, cell indices)."""
+    cell = []
+    for d in range(3):
+        c = np.floor((np.asarray(pos[d], dtype=np.float64) - np.float64(plo[d])) * np.float64(dinv[d])).astype(np.int64)
+        if wrap[d]:
+            c = np.where(c < 0, c + ncell[d], np.where(c >= ncell[d], c - ncell[d], c))
+        cell.append(np.clip(c, 0, ncell[d] - 1))
+    T = 8
+    nt = [(m + T - 1) // T for m in ncell]
+    tile = cell[0] // T + nt[0] * (cell[1] // T + nt[1] * (cell[2] // T))
+    kt = cell[2] % T
+    return tile * T ** 3 + cell[0] % T + T * ((kt & 1) + 2 * (cell[1] % T + T * (kt >> 1))), cell
+
+
 def yee_dt(dx, cfl=1.0):
     return cfl / (np.sqrt(np.sum(1.0 / np.asarray(dx) ** 2)) * plasma.C_LIGHT)
 

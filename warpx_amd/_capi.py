@@ -309,9 +309,11 @@ _PRODUCT_SIGS = {
     "enforce_periodic_sorted": (C.c_int, [_PPV, _D3, _D3, _I3, C.c_void_p, C.c_int32, C.c_void_p]),
     "workspace_set_deposit_accumulator": (C.c_int, [C.c_void_p, C.c_int32]),
     "workspace_set_streaming_plasma": (C.c_int, [C.c_void_p, C.c_int32]),
+    "workspace_last_stragglers": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "sim_set_deposit_accumulator": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
 }
 ACC_FP64, ACC_FP32 = 0, 1
+TILE_GATHER, TILE_DEPOSIT = 0, 1
 PUSH_SORT_COUNT, PUSH_SORT_SCATTER = 1, 2
 
 # the library's own transport (rccl_comm.hip): product only

@@ -42,6 +42,21 @@ wxa_status wxa_workspace_set_streaming_plasma(wxa_workspace* ws, int32_t on) {
     return WXA_OK;
 }
 
+wxa_status wxa_workspace_last_stragglers(wxa_workspace* ws, int32_t tile_kernel, int64_t* count) {
+    WXA_REQUIRE(ws && count, "null argument");
+    WXA_REQUIRE(tile_kernel == WXA_TILE_GATHER || tile_kernel == WXA_TILE_DEPOSIT, "tile_kernel must be WXA_TILE_GATHER or WXA_TILE_DEPOSIT");
+    *count = 0;
+    const unsigned flips = tile_kernel == WXA_TILE_GATHER ? ws->gather_flips : ws->deposit_flips;
+    if (!ws->flip_ready || flips == 0) return WXA_OK;   // no launch yet
+    // launch n counted in slot n & 1 (wxa::flip_counter); the next launch zeroes it
+    const unsigned* slot = (const unsigned*)ws->counters.p + (tile_kernel == WXA_TILE_GATHER ? wxa::CW_GATHER : wxa::CW_DEPOSIT) + ((flips - 1u) & 1u);
+    unsigned n = 0;
+    WXA_HIP_CHECK(hipDeviceSynchronize());
+    WXA_HIP_CHECK(hipMemcpy(&n, slot, sizeof(n), hipMemcpyDeviceToHost));
+    *count = (int64_t)n;
+    return WXA_OK;
+}
+
 wxa_status wxa_workspace_set_repeated_plasma_lens(wxa_workspace* ws, const wxa_repeated_plasma_lens* lens) {
     WXA_REQUIRE(ws && lens, "null argument");
     WXA_REQUIRE(lens->n_lenses >= 0, "negative number of lenses");
