@@ -33,19 +33,23 @@ def _run(args, extra_env=None, timeout=900):
 
 def test_kernel_parity_tests_pass_on_the_cpu_execution_model():
     """Every test of tests/test_kernels_gpu.py, including those still gated on the GPU because no MI355X has
-    run them yet (WXA_UNVERIFIED_GPU_TESTS), and the geometry sweep of tests/test_geometry_gpu.py (374 cases)."""
-    out = _run(["tests/test_kernels_gpu.py", "tests/test_geometry_gpu.py"], {"WXA_UNVERIFIED_GPU_TESTS": "1"})
+    run them yet (WXA_UNVERIFIED_GPU_TESTS), the geometry sweep of tests/test_geometry_gpu.py (374 cases) and the pushers
+    against their model in tests/test_pushers_gpu.py (96 cases)."""
+    out = _run(["tests/test_kernels_gpu.py", "tests/test_geometry_gpu.py", "tests/test_pushers_gpu.py"],
+               {"WXA_UNVERIFIED_GPU_TESTS": "1"})
     summary = out.strip().splitlines()[-1]
     assert " passed" in summary and "failed" not in summary, summary
-    assert int(summary.split(" passed")[0].split()[-1]) >= 110 + 374, summary
+    assert int(summary.split(" passed")[0].split()[-1]) >= 110 + 374 + 96, summary
 
 
 def test_kernel_tests_with_guard_pages_and_fma_contraction():
     """The same tests on the build that contracts a*b+c like hipcc does for device code, every "device" buffer
     (the tests' and the library's) ending on an inaccessible page: no kernel touches memory outside the arrays it
     is handed, and no comparison with the oracle relies on unfused arithmetic.  With tests/test_geometry_gpu.py: this is
-    where a staging loop that steps outside a small or offset box faults."""
-    _run(["tests/test_kernels_gpu.py", "tests/test_geometry_gpu.py"], {"HIPCPU_GUARD_PAGES": "1", "WXA_HIP_ON_CPU_FMA": "1"})
+    where a staging loop that steps outside a small or offset box faults.  With tests/test_pushers_gpu.py: the pushers'
+    gates pay for contraction, and the stragglers there sit in the guard cells."""
+    _run(["tests/test_kernels_gpu.py", "tests/test_geometry_gpu.py", "tests/test_pushers_gpu.py"],
+         {"HIPCPU_GUARD_PAGES": "1", "WXA_HIP_ON_CPU_FMA": "1"})
 
 
 def test_short_step_parity_on_the_cpu_execution_model():

@@ -1676,11 +1676,22 @@ def test_higuera_cary_push_with_external_fields(oracle, product, order, sort, pu
         a, b = pd.to_numpy(), pc.to_numpy()
         for row in range(7):
             assert np.max(np.abs(a[row] - b[row])) <= 1e-12 * max(np.max(np.abs(b[row])), 1e-300), (move, row)
-    # without the workspace the external fields are zero: a different result
+        if move:
+            with_ext = b
+    # without the workspace the external fields are zero: PushPX of the grid fields alone, and not the result above
+    # (the external E alone kicks by 5e-3 of the momentum scale)
     pz = ParticleArrays.from_numpy(parts, DEV)
     product.gather_push(C.byref(pz.view), field_triplet(Ed), field_triplet(Bd), C.byref(g), q, m, dt, order, 1,
                         pusher, None)
     _sync(product)
+    po = ParticleArrays.from_numpy(parts, "cpu")
+    oracle.gather_push(C.byref(po.view), field_triplet(E), field_triplet(B), C.byref(g), q, m, dt, order, 1, pusher, None)
+    a, b = pz.to_numpy(), po.to_numpy()
+    unsorted = pd.ids_to_numpy() - 1
+    for row in range(7):
+        assert np.max(np.abs(a[row] - b[row])) <= 1e-12 * max(np.max(np.abs(b[row])), 1e-300), row
+    for row in (4, 5, 6):
+        assert np.max(np.abs(a[row][unsorted] - with_ext[row])) > 1e-4 * np.max(np.abs(with_ext[row])), row
     product.workspace_destroy(ws)
 
 
